@@ -1,12 +1,17 @@
 """Flagship training-step benchmark (driver contract).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Measures the whole-job training throughput (tokens/s over all N GPUs) of the
 headline config: GPT-1.3B, ZeRO-1, bf16, ALiBi, block_size 2048, synthetic
 data, random-init weights (BASELINE.json). Weak scaling: per-GPU batch is
 fixed as N grows. For N > 1 the driver launches this script under
 torch.distributed.run with one rank per GPU over RCCL.
+
+A plain run sets up, warms up, times K steps and prints one JSON result line.
+--dump-outputs DIR additionally writes what the last timed step produced
+(see dump_outputs). --full is where any measurement beyond the headline
+figure belongs; there is none today, so it changes nothing.
 """
 
 from __future__ import annotations
@@ -16,6 +21,7 @@ import json
 import os
 import time
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -43,7 +49,52 @@ def parse():
         "curriculum active (reference conf/config.yaml:3,22, main_zero.py:481-493); "
         "fixed global batch => strong scaling",
     )
-    return p.parse_args()
+    p.add_argument(
+        "--dump-outputs",
+        metavar="DIR",
+        default=None,
+        help="after the timed steps, write the last step's outputs as DIR/<name>.npy",
+    )
+    p.add_argument(
+        "--full",
+        action="store_true",
+        help="also run every secondary measurement (none exist yet: the "
+        "headline figure is all this benchmark measures)",
+    )
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be >= 1")
+    if args.warmup < 0:
+        p.error("--warmup must be >= 0")
+    return args
+
+
+DUMP_SAMPLE_PER_PARAM = 4096  # elements sampled from each parameter tensor
+
+
+@torch.no_grad()
+def dump_outputs(out_dir, metrics, model):
+    """Write what the last timed train_step handed back, one .npy per name.
+
+    A caller of TrainEngine.train_step receives the metrics dict and the
+    model updated in place: each metric goes out as a 1-element float64
+    array, and the updated (bf16 working) parameters as a fixed, seeded
+    sample of DUMP_SAMPLE_PER_PARAM elements per tensor, concatenated in
+    named_parameters() order, float32 (~0.5M values for the 1.3B model; the
+    full set would be 5 GB).
+    """
+    os.makedirs(out_dir, exist_ok=True)
+    for k in ("train/loss", "train/grad_norm", "lr"):
+        name = k.split("/")[-1]
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.array([metrics[k]], dtype=np.float64))
+    gen = torch.Generator(device="cpu").manual_seed(4321)
+    parts = []
+    for _, p in model.named_parameters():
+        flat = p.detach().reshape(-1)
+        n = min(DUMP_SAMPLE_PER_PARAM, flat.numel())
+        idx = torch.randint(0, flat.numel(), (n,), generator=gen).to(flat.device)
+        parts.append(flat[idx].float().cpu())
+    np.save(os.path.join(out_dir, "params_sample.npy"), torch.cat(parts).numpy())
 
 
 def main():
@@ -116,7 +167,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        engine.train_step(batches[i % 2])
+        metrics = engine.train_step(batches[i % 2])
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -126,6 +177,9 @@ def main():
         t = torch.tensor([elapsed], device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, metrics, model)
 
     ms_per_step = elapsed / args.steps * 1000.0
     tokens_per_step = args.batch * seq * world  # whole-job
