@@ -32,6 +32,9 @@ def main():
     p.add_argument("--T", type=int, default=2048)
     p.add_argument("--D", type=int, default=128)
     p.add_argument("--dropout", type=float, default=0.0)
+    p.add_argument("--fused", type=int, default=-1,
+                   help="backward scheme: -1 process default (ZTA_BWD_FUSED), "
+                        "0 two-kernel dq + dkdv, 1 fused kernel")
     args = p.parse_args()
     B, H, T, D = args.B, args.H, args.T, args.D
     dev = torch.device("cuda")
@@ -47,8 +50,8 @@ def main():
     o, lse = ext.attn_fwd(qkv, slopes, H, args.dropout, 7)
     do = torch.randn_like(o)
     bwd_flops = fwd_flops * 2.5  # 5 GEMMs vs 2
-    t = bench(lambda: ext.attn_bwd(do, qkv, slopes, o, lse, H, args.dropout, 7))
-    print(f"bwd : {t*1e3:8.3f} ms  {bwd_flops/t/1e12:7.1f} TF/s")
+    t = bench(lambda: ext.attn_bwd(do, qkv, slopes, o, lse, H, args.dropout, 7, args.fused))
+    print(f"bwd : {t*1e3:8.3f} ms  {bwd_flops/t/1e12:7.1f} TF/s  (fused={args.fused})")
 
 
 if __name__ == "__main__":

@@ -1,7 +1,23 @@
-// Flash attention backward for gfx950 (CDNA4 MFMA): FA2-style two-kernel
-// scheme with P recomputed from the saved per-row LSE — no O(T^2) tensor is
-// ever materialized (the reference's autograd attention backward
-// re-materializes the dense probs; SURVEY.md §2.3 "Backward of all above").
+// Flash attention backward for gfx950 (CDNA4 MFMA) with P recomputed from
+// the saved per-row LSE — no O(T^2) tensor is ever materialized (the
+// reference's autograd attention backward re-materializes the dense probs;
+// SURVEY.md §2.3 "Backward of all above"). Two schemes:
+//
+// FUSED (head_dim 128, the default there): delta kernel, then ONE
+// key-stationary kernel (flash_bwd_fused_kernel) that computes S and dP
+// once and forms all of dV, dK and dQ from them — five MFMA products per
+// tile pair instead of the two-kernel scheme's seven, one softmax / dropout
+// regeneration instead of two. dQ is summed across the key blocks of a
+// (b, h) with no-return f32 atomics into an f32 scratch (zeroed per call),
+// then converted to bf16 into the q columns of dqkv. Everything runs on the
+// caller's stream. f32 atomics make dQ differ in the last bits from run to
+// run; dK and dV are bitwise reproducible.
+//
+// TWO-KERNEL (all head dims; bitwise reproducible): the FA2-style dQ and
+// dKdV kernels below. ZTA_BWD_FUSED=0 selects it process-wide,
+// ZTA_BWD_FUSED=1 the fused scheme; the binding's trailing `fused` argument
+// (-1 default / 0 / 1) selects per call. Head dims other than 128 always
+// take the two-kernel path.
 //
 //   delta[b,h,i] = sum_d dO * O                  (delta kernel)
 //   dQ kernel : per 256-row Q block (8 waves x 32 rows), loop 64-key tiles:
@@ -35,6 +51,8 @@
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 #include <torch/extension.h>
 
+#include <type_traits>
+
 namespace {
 
 using attn::NW;
@@ -50,6 +68,8 @@ constexpr float NEG_INF = -3.0e38f;
 // with scale2/slope2/lse2 pre-multiplied by log2(e) — raw v_exp_f32, no
 // hidden per-element multiply (matches the forward's folded softmax).
 constexpr float LOG2E = 1.4426950408889634f;
+// Backward scheme when ZTA_BWD_FUSED is unset (see the file header).
+constexpr bool BWD_FUSED_DEFAULT = true;
 
 // ---------------------------------------------------------------------------
 // dout/o are (B, T, C); delta is (B, H, T): row index r = (b*H + h)*T + t
@@ -750,6 +770,314 @@ __global__ __launch_bounds__(256, 1) void flash_dkdv4_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// Fused backward (D = 128): one key-stationary kernel, five products per tile
+// pair. A workgroup owns 256 keys of one (b, h): 4 waves x 64 keys (two
+// 32-key lane groups), dK/dV accumulators and V fragments resident, and
+// sweeps 32-row query slices from its first key to T. Per slice each wave
+// computes S, dP, P and dS once for its keys, accumulates dV/dK as in
+// flash_dkdv4_kernel, and drops dS (bf16 A-fragment words) into a shared
+// [key][q] LDS tile. After an LDS-only barrier wave w forms the slice's dQ
+// columns [32w, 32w+32) over all active keys of the block (A = transpose
+// reads of the dS tile, B = transpose reads of the block's K image) and
+// adds it into the f32 scratch with no-return atomics: one accumulator
+// register is two 128 B row segments. No workgroup waits on another.
+// LDS: K image 256x[256B] | q0 do0 q1 do1 32x[256B] | dS 2x 256x[64B] |
+//      (lse, delta) 2x 64 f32 = 128.5 KiB. No vector-memory load inside the
+// slice loop returns to a register (Q, dO, lse and delta all arrive by
+// LDS-DMA): a register load would make the compiler wait on vmcnt, which
+// retires in order and would drain the dQ atomics issued before it.
+// Registers: the 256 dK/dV accumulators fill the accumulation file, so the
+// transient S / dP / dQ tiles run through attn::mfma_sdp2 / mfma_quad_acc
+// (arch-VGPR destinations). 256 + 256 registers, no scratch; re-check with
+// -Rpass-analysis=kernel-resource-usage after any edit.
+// ---------------------------------------------------------------------------
+constexpr int FKB = 256;  // keys per fused-backward workgroup
+constexpr int FQS = 32;   // query rows per slice
+constexpr size_t FUSED_SMEM =
+    (size_t)(FKB * 128 + 4 * FQS * 128 + 2 * FKB * 32) * sizeof(uint16_t) +
+    4 * FQS * sizeof(float);
+
+template <int D>
+__global__ __launch_bounds__(256, 1) void flash_bwd_fused_kernel(
+    const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ dout,
+    const float* __restrict__ lse, const float* __restrict__ delta,
+    const float* __restrict__ slopes, uint16_t* __restrict__ dqkv,
+    float* __restrict__ dq32, int H, int T, int C, float scale, float p_drop,
+    uint32_t seed) {
+  static_assert(D == 128, "fused backward covers head_dim 128 only");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  uint16_t* k_img = (uint16_t*)smem;
+  uint16_t* lds0 = k_img + FKB * 128;        // [q0 | do0 | q1 | do1]
+  uint16_t* ds0 = lds0 + 4 * FQS * 128;      // two [256 keys][32 q] dS tiles
+  float* stats0 = (float*)(ds0 + 2 * FKB * 32);  // two [lse 32 | delta 32]
+
+  const int bh = blockIdx.x;  // grid: (BH, key blocks), heaviest block first
+  const int h = bh % H;
+  const int QS = 3 * C;
+  const long base = (long)(bh / H) * T * QS + h * D;
+  const long kbase = base + C;
+  const long vbase = base + 2 * C;
+  const long dobase = (long)(bh / H) * T * C + h * D;
+  const int k0 = blockIdx.y * FKB;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  const int li = lane & 31, hi = lane >> 5;
+  const int kw = k0 + wave * 64;  // this wave's first key
+  const float slope = slopes[h];
+  const float scale2 = scale * LOG2E;
+  const float slope2 = slope * LOG2E;
+  const uint32_t thr = (uint32_t)(p_drop * 256.0f + 0.5f);
+  const float inv_keep = thr ? 256.0f / (256.0f - (float)thr) : 1.0f;
+
+  constexpr int KS = D / 16;
+  constexpr int DB = D / 32;
+
+  bf16x8 v_frag[2][KS];
+#pragma unroll
+  for (int g = 0; g < 2; ++g) {
+    const int kj = kw + 32 * g + li;
+#pragma unroll
+    for (int s = 0; s < KS; ++s)
+      v_frag[g][s] = kj < T ? *reinterpret_cast<const bf16x8*>(
+                                  &qkv[vbase + (long)kj * QS + s * 16 + 8 * hi])
+                            : bf16x8{};
+  }
+
+  f32x16 dk_acc[2][DB], dv_acc[2][DB];
+#pragma unroll
+  for (int g = 0; g < 2; ++g)
+#pragma unroll
+    for (int d = 0; d < DB; ++d) {
+      dk_acc[g][d] = f32x16{};
+      dv_acc[g][d] = f32x16{};
+    }
+
+#pragma unroll
+  for (int i = 0; i < FKB / TB; ++i)
+    attn::glds_stage<D, 4>(qkv, kbase, QS, k0 + TB * i, T, k_img + i * TB * 128);
+  attn::glds_stage<D, 4, FQS>(qkv, base, QS, k0, T, lds0);
+  attn::glds_stage<D, 4, FQS>(dout, dobase, C, k0, T, lds0 + FQS * 128);
+  if (wave == 0) attn::glds_stats32(lse, delta, (long)bh * T, k0, T, stats0);
+
+  // Settle the V loads here: left pending into the loop, their first use
+  // would carry a vmcnt(0) in every slice and drain the dQ atomics with it.
+#pragma unroll
+  for (int g = 0; g < 2; ++g)
+#pragma unroll
+    for (int s = 0; s < KS; ++s) asm volatile("" : "+v"(v_frag[g][s]));
+
+  const int kend64 = min(FKB, (T - k0 + 63) & ~63);  // keys of this block, /64 up
+  float* const dq_col = dq32 + ((long)(bh / H) * T) * C + h * D + 32 * wave;
+
+  // One loop over 32-row query slices, each staged one slice ahead into
+  // the other (Q, dO, stats) buffer. A single loop body (no per-slice
+  // specialization) keeps the 256 resident accumulators in one live range
+  // each.
+#pragma unroll 1
+  for (int q32 = k0; q32 < T; q32 += FQS) {
+    // Loop-local opaque lane id: LDS addresses derived from it are
+    // recomputed per slice instead of being hoisted out of the loop, where
+    // a few hundred lane constants would be spilled around it.
+    int lv = lane;
+    asm volatile("" : "+v"(lv));
+    const int li = lv & 31, hi = lv >> 5;
+    const int sl = (q32 - k0) >> 5;  // slice number within the block
+    const int cur = sl & 1;
+    const uint16_t* q_lds = lds0 + cur * (2 * FQS * 128);
+    const uint16_t* do_lds = q_lds + FQS * 128;
+    const float* lse_s = stats0 + cur * (2 * FQS);
+    const float* delta_s = lse_s + FQS;
+    uint16_t* ds_t = ds0 + cur * (FKB * 32);
+    // slice-ready barrier: waits this slice's LDS-DMA (first time: all of
+    // it, K image included) and frees the buffers the next prefetch
+    // overwrites. Later slices leave the previous slice's dQ atomics in
+    // flight: a slice that has a successor lies wholly below T, so each wave
+    // issued exactly 16 atomic instructions after that DMA group.
+    if (sl == 0)
+      attn::tile_barrier<0>();
+    else
+      attn::tile_barrier<16>();
+    if (q32 + FQS < T) {
+      uint16_t* nxt = lds0 + (cur ^ 1) * (2 * FQS * 128);
+      attn::glds_stage<D, 4, FQS>(qkv, base, QS, q32 + FQS, T, nxt, lv);
+      attn::glds_stage<D, 4, FQS>(dout, dobase, C, q32 + FQS, T, nxt + FQS * 128, lv);
+      if (wave == 0)
+        attn::glds_stats32(lse, delta, (long)bh * T, q32 + FQS, T,
+                           stats0 + (cur ^ 1) * (2 * FQS), lv);
+    }
+
+    // Every wave runs every slice, also the few diagonal slices that lie
+    // wholly above its keys (they contribute p = 0): the waves meet at the
+    // barrier below anyway, and a branch around the accumulation would
+    // split the live ranges of the 256 resident accumulators.
+    {
+      // Key groups run one after the other through S/dP and the softmax
+      // (scheduling fences keep the register peak at one group's worth);
+      // K rows come from the K image, V fragments are resident.
+      attn::TrQuad qq[2];
+      bf16x8 pa[2][2], dsa[2][2];
+#pragma unroll
+      for (int g = 0; g < 2; ++g) {
+        // S = Q K^T ; dP = dO V^T  (C[i=q][j=key])
+        // (arch-VGPR accumulators: attn::mfma_sdp2, two k-steps a statement)
+        f32x16 s_acc, dp_acc;
+        const int krow = wave * 64 + g * 32 + li;
+#pragma unroll
+        for (int s4 = 0; s4 < KS; s4 += 2) {
+          bf16x8 qa[2], da[2], kb[2];
+#pragma unroll
+          for (int s = 0; s < 2; ++s) {
+            const int kk = (s4 + s) * 16 + 8 * hi;
+            qa[s] = *reinterpret_cast<const bf16x8*>((char*)q_lds + swz(li, li * 256 + kk * 2));
+            da[s] = *reinterpret_cast<const bf16x8*>((char*)do_lds + swz(li, li * 256 + kk * 2));
+            kb[s] = *reinterpret_cast<const bf16x8*>((char*)k_img + swz(krow, krow * 256 + kk * 2));
+          }
+          if (s4 == 0)
+            attn::mfma_sdp2<true>(s_acc, dp_acc, qa, da, kb, &v_frag[g][s4]);
+          else
+            attn::mfma_sdp2<false>(s_acc, dp_acc, qa, da, kb, &v_frag[g][s4]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+
+        // d-block 0's transpose reads hide under the last group's softmax;
+        // drained with a full lgkmcnt(0) (compiler DS ops interleave here,
+        // see flash_dkdv4_kernel).
+        if (g == 1) attn::tr_quad_issue(do_lds, q_lds, 0, 0, &qq[0], lv);
+
+        float p_pv[16], ds[16];
+        const int kj = kw + 32 * g + li;
+        auto softmax = [&](auto drop) {
+          // drop_bits32 with its row term formed incrementally (uint32 wrap
+          // arithmetic, bit-identical): (bh*T + q32 + row) * 0x9e3779b9
+          const uint32_t hrow0 = (uint32_t)(bh * T + q32 + 4 * hi) * 0x9e3779b9u;
+          const uint32_t hkey = seed ^ ((uint32_t)(kj >> 2) * 0x85ebca6bu);
+          const int kshift = 8 * (kj & 3);
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int row = (r & 3) + 8 * (r >> 2) + 4 * hi;
+            const int qi = q32 + row;
+            const float lq = lse_s[row] * LOG2E;  // log2 domain
+            const float dq_ = delta_s[row];
+            const bool masked = kj > qi || kj >= T || qi >= T;
+            const float x = masked ? -3.0e38f
+                                   : s_acc[r] * scale2 + slope2 * (float)(kj - qi) - lq;
+            const float p = __builtin_amdgcn_exp2f(x);  // raw v_exp_f32; exp2(-3e38) = 0
+            float dp = dp_acc[r];
+            float ppv = p;
+            if (decltype(drop)::value) {
+              const uint32_t bits =
+                  mix32(hkey ^ (hrow0 + (uint32_t)((r & 3) + 8 * (r >> 2)) * 0x9e3779b9u));
+              const bool keep = ((bits >> kshift) & 0xffu) >= thr;
+              dp = keep ? dp * inv_keep : 0.f;
+              ppv = keep ? p * inv_keep : 0.f;
+            }
+            p_pv[r] = ppv;
+            ds[r] = scale * p * (dp - dq_);
+          }
+        };
+        if (thr)
+          softmax(std::true_type{});
+        else
+          softmax(std::false_type{});
+        c_to_a_frags(p_pv, pa[g]);  // A[i=key][k=q]
+        c_to_a_frags(ds, dsa[g]);
+        // the same words are the dS tile's [key][q] rows: 16 B per lane
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2)
+          *reinterpret_cast<bf16x8*>((char*)ds_t + krow * 64 + (s2 * 16 + 8 * hi) * 2) = dsa[g][s2];
+        __builtin_amdgcn_sched_barrier(0);
+      }
+
+      attn::tr_quad_wait<0>(&qq[0]);
+#pragma unroll
+      for (int d = 0; d < DB; ++d) {
+        if (d + 1 < DB)
+          attn::tr_quad_issue(do_lds, q_lds, 0, (d + 1) * 32, &qq[(d + 1) & 1], lv);
+        attn::TrQuad& t = qq[d & 1];
+        if (d > 0) {
+          if (d + 1 < DB)
+            attn::tr_quad_wait<8>(&t);
+          else
+            attn::tr_quad_wait<0>(&t);
+        }
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+          dv_acc[g][d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[g][0], t.x.a, dv_acc[g][d], 0, 0, 0);
+          dv_acc[g][d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[g][1], t.x.b, dv_acc[g][d], 0, 0, 0);
+          dk_acc[g][d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dsa[g][0], t.y.a, dk_acc[g][d], 0, 0, 0);
+          dk_acc[g][d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dsa[g][1], t.y.b, dk_acc[g][d], 0, 0, 0);
+        }
+      }
+    }
+
+    // dS tile complete: all 256 key rows written (zeros where masked)
+    attn::lds_barrier();
+
+    // dQ[32 q][32w..32w+32) = dS[q][keys] K[keys][d] over those keys, two
+    // 32-key steps per trip (software-pipelined transpose reads).
+    const int nkp = min(kend64, (q32 + 32 - k0 + 63) & ~63) >> 5;  // even, >= 2
+    f32x16 dq = f32x16{};
+    attn::TrQuad kq[2];
+    attn::tr_dsk_issue(ds_t, k_img, 0, 32 * wave, &kq[0], lv);
+#pragma unroll 1
+    for (int kp = 0; kp < nkp; kp += 2) {
+      attn::tr_dsk_issue(ds_t, k_img, (kp + 1) * 32, 32 * wave, &kq[1], lv);
+      attn::tr_quad_wait<8>(&kq[0]);
+      attn::mfma_quad_acc(dq, kq[0]);
+      if (kp + 2 < nkp) {
+        attn::tr_dsk_issue(ds_t, k_img, (kp + 2) * 32, 32 * wave, &kq[0], lv);
+        attn::tr_quad_wait<8>(&kq[1]);
+      } else {
+        attn::tr_quad_wait<0>(&kq[1]);
+      }
+      attn::mfma_quad_acc(dq, kq[1]);
+    }
+    // one register = rows crow(r,0) and crow(r,1), 128 B each; left in flight
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int qr = q32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+      if (qr < T) unsafeAtomicAdd(dq_col + (long)qr * C + li, dq[r]);
+    }
+  }
+
+  // epilogue: dK/dV rows crow(r,hi) of each key group
+#pragma unroll
+  for (int g = 0; g < 2; ++g)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int kr = kw + 32 * g + (r & 3) + 8 * (r >> 2) + 4 * hi;
+      if (kr >= T) continue;
+#pragma unroll
+      for (int d = 0; d < DB; ++d) {
+        dqkv[kbase + (long)kr * QS + d * 32 + li] = f32_to_bf16(dk_acc[g][d][r]);
+        dqkv[vbase + (long)kr * QS + d * 32 + li] = f32_to_bf16(dv_acc[g][d][r]);
+      }
+    }
+}
+
+// f32 dQ scratch (B, T, C) -> bf16 q columns of dqkv (row stride 3C); eight
+// elements per thread: two 16 B loads, one 16 B store. C % 8 == 0.
+__global__ void dq_convert_kernel(const float* __restrict__ dq32,
+                                  uint16_t* __restrict__ dqkv, long rows, int C) {
+  const int cpr = C / 8;  // 8-element chunks per row
+  const long n = rows * cpr;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (long)gridDim.x * blockDim.x) {
+    const long row = i / cpr;
+    const int c = (int)(i % cpr) * 8;
+    const f32x4 a = *reinterpret_cast<const f32x4*>(&dq32[row * C + c]);
+    const f32x4 b = *reinterpret_cast<const f32x4*>(&dq32[row * C + c + 4]);
+    s16x8 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      o[j] = (short)f32_to_bf16(a[j]);
+      o[4 + j] = (short)f32_to_bf16(b[j]);
+    }
+    *reinterpret_cast<s16x8*>(&dqkv[row * 3 * C + c]) = o;
+  }
+}
+
 // dq and dkdv are independent (disjoint column ranges of dqkv) and both
 // stall-bound at one 512-thread block per CU — run them CONCURRENTLY on two
 // streams so their blocks co-reside (227 + 256 VGPR and 32 + 64.5 KB LDS
@@ -828,11 +1156,47 @@ void launch_bwd(const at::Tensor& qkv, const at::Tensor& dout, const at::Tensor&
   (void)hipStreamWaitEvent(stream, bwd_event(1), 0);
 }
 
+// Fused path, all on the caller's stream: (scratch already zeroed, delta
+// done) fused kernel, then the f32 -> bf16 dQ convert.
+void launch_bwd_fused(const at::Tensor& qkv, const at::Tensor& dout,
+                      const at::Tensor& lse, const at::Tensor& delta,
+                      const at::Tensor& slopes, at::Tensor& dqkv, at::Tensor& dq32,
+                      int B, int H, int T, int C, float scale, float p_drop,
+                      uint32_t seed, hipStream_t stream) {
+  static const bool attr_ok = [] {
+    return hipFuncSetAttribute((const void*)flash_bwd_fused_kernel<128>,
+                               hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)FUSED_SMEM) == hipSuccess;
+  }();
+  TORCH_CHECK(attr_ok, "attn_bwd: fused kernel needs ", FUSED_SMEM, " B of LDS");
+  dim3 grid(B * H, (T + FKB - 1) / FKB);
+  hipLaunchKernelGGL(flash_bwd_fused_kernel<128>, grid, dim3(256), FUSED_SMEM, stream,
+                     (const uint16_t*)qkv.data_ptr(), (const uint16_t*)dout.data_ptr(),
+                     lse.data_ptr<float>(), delta.data_ptr<float>(),
+                     slopes.data_ptr<float>(), (uint16_t*)dqkv.data_ptr(),
+                     dq32.data_ptr<float>(), H, T, C, scale, p_drop, seed);
+  TORCH_CHECK(hipGetLastError() == hipSuccess, "attn_bwd: fused kernel launch failed");
+  const long rows = (long)B * T;
+  hipLaunchKernelGGL(dq_convert_kernel, dim3(capped_grid(rows * (C / 8), 256)),
+                     dim3(256), 0, stream, dq32.data_ptr<float>(),
+                     (uint16_t*)dqkv.data_ptr(), rows, C);
+}
+
+// Process-wide default of the backward scheme: ZTA_BWD_FUSED=0 selects the
+// two-kernel path, ZTA_BWD_FUSED=1 the fused kernel.
+inline bool bwd_fused_default() {
+  static const bool v = [] {
+    const char* e = getenv("ZTA_BWD_FUSED");
+    return e ? e[0] != '0' : BWD_FUSED_DEFAULT;
+  }();
+  return v;
+}
+
 }  // namespace
 
 std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor qkv, at::Tensor slopes,
                                  at::Tensor o, at::Tensor lse, int64_t H_,
-                                 double p_drop, int64_t seed) {
+                                 double p_drop, int64_t seed, int64_t fused) {
   TORCH_CHECK(qkv.is_cuda() && qkv.is_contiguous() && qkv.dim() == 3);
   TORCH_CHECK(dout.is_contiguous() && dout.dim() == 3);
   const int B = qkv.size(0), T = qkv.size(1), H = (int)H_;
@@ -843,6 +1207,11 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor qkv, at::Tensor slo
   auto sl = slopes.to(at::kFloat).contiguous();
   const float scale = 1.0f / sqrtf((float)D);
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
+  // fused < 0: process default (ZTA_BWD_FUSED); head dims the fused kernel
+  // does not cover take the two-kernel path.
+  const bool use_fused = D == 128 && (fused < 0 ? bwd_fused_default() : fused != 0);
+  at::Tensor dq32;
+  if (use_fused) dq32 = at::zeros({B, T, C}, qkv.options().dtype(at::kFloat));
   {
     const long rows = (long)B * H * T;
     const int block = 256;
@@ -857,6 +1226,11 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor qkv, at::Tensor slo
                          (const uint16_t*)o.data_ptr(), delta.data_ptr<float>(),
                          rows, H, T, C, D);
     }
+  }
+  if (use_fused) {
+    launch_bwd_fused(qkv, dout, lse, delta, sl, dqkv, dq32, B, H, T, C, scale,
+                     (float)p_drop, (uint32_t)seed, stream);
+    return {dqkv};
   }
   switch (D) {
     case 32: launch_bwd<32>(qkv, dout, lse, delta, sl, dqkv, B, H, T, C, scale, (float)p_drop, (uint32_t)seed, stream); break;

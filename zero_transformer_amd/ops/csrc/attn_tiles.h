@@ -132,9 +132,10 @@ ZTA_DEV TrQuad tr_frag_quad(const uint16_t* lds_x, const uint16_t* lds_y, int k0
 // issued after this group) is correct even if the compiler interleaves its
 // own LDS ops — any overcount only waits longer. (SMEM also counts in
 // lgkmcnt and completes out of order, but none is live in these loops.)
+// `l` is the lane id; a kernel whose tile loop must not carry hoisted
+// per-lane addresses (register pressure) passes a loop-local opaque copy.
 ZTA_DEV void tr_quad_issue(const uint16_t* lds_x, const uint16_t* lds_y, int k0,
-                           int j0, TrQuad* out) {
-  const int l = threadIdx.x & 63;
+                           int j0, TrQuad* out, int l = threadIdx.x & 63) {
   const int colb = (j0 + (l & 16) + 4 * (l & 3)) * 2;
   const int rb = 8 * (l >> 5) + ((l >> 2) & 3);
   int ax[4], ay[4];
@@ -162,6 +163,112 @@ ZTA_DEV void tr_quad_issue(const uint16_t* lds_x, const uint16_t* lds_y, int k0,
         "=&v"(u->d[4]), "=&v"(u->d[5]), "=&v"(u->d[6]), "=&v"(u->d[7])
       : "v"(ax[0]), "v"(ax[1]), "v"(ax[2]), "v"(ax[3]), "v"(ay[0]), "v"(ay[1]),
         "v"(ay[2]), "v"(ay[3]));
+}
+
+// Quad for the fused backward's dQ = dS K product (same issue / counted-wait
+// contract as tr_quad_issue, drained with tr_quad_wait): x is the A-fragment
+// pair of dS, transpose-read from the workgroup's bf16 dS tile
+// [key][32 q rows] (64 B rows, unswizzled — lane l receives
+// tile[k0 + 8*(l>>5) + e][l&31], i.e. A[i = q][k = key]); y is the
+// B-fragment pair of K, columns j0..j0+31, from the swizzled 256 B-row K
+// image. Keys k0..k0+15 land in .a, k0+16..k0+31 in .b.
+ZTA_DEV void tr_dsk_issue(const uint16_t* ds_tile, const uint16_t* k_img, int k0,
+                          int j0, TrQuad* out, int l = threadIdx.x & 63) {
+  const int cq = ((l & 16) + 4 * (l & 3)) * 2;
+  const int colb = (j0 + (l & 16) + 4 * (l & 3)) * 2;
+  const int rb = 8 * (l >> 5) + ((l >> 2) & 3);
+  int ax[4], ay[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int row = k0 + 16 * (i >> 1) + 4 * (i & 1) + rb;
+    ax[i] = (int)(size_t)((const char*)ds_tile + row * 64 + cq);
+    ay[i] = (int)(size_t)((const char*)k_img + row * 256 + (colb ^ ((row & 7) << 4)));
+  }
+  union U {
+    i32x2 d[8];
+    TrQuad f;
+  }* u = (union U*)out;
+  asm volatile(
+      "ds_read_b64_tr_b16 %0, %8\n\t"
+      "ds_read_b64_tr_b16 %1, %9\n\t"
+      "ds_read_b64_tr_b16 %2, %10\n\t"
+      "ds_read_b64_tr_b16 %3, %11\n\t"
+      "ds_read_b64_tr_b16 %4, %12\n\t"
+      "ds_read_b64_tr_b16 %5, %13\n\t"
+      "ds_read_b64_tr_b16 %6, %14\n\t"
+      "ds_read_b64_tr_b16 %7, %15"
+      : "=&v"(u->d[0]), "=&v"(u->d[1]), "=&v"(u->d[2]), "=&v"(u->d[3]),
+        "=&v"(u->d[4]), "=&v"(u->d[5]), "=&v"(u->d[6]), "=&v"(u->d[7])
+      : "v"(ax[0]), "v"(ax[1]), "v"(ax[2]), "v"(ax[3]), "v"(ay[0]), "v"(ay[1]),
+        "v"(ay[2]), "v"(ay[3]));
+}
+
+// Workgroup barrier that also waits this wave's vector-memory operations
+// down to the N youngest (vmcnt retires in issue order; LDS-DMA loads, plain
+// loads, stores and no-return atomics all count): the wave's LDS-DMA tile
+// lands while N later atomics stay in flight. N must not exceed the number
+// of vector-memory instructions the wave issued after the DMA group.
+template <int N>
+ZTA_DEV void tile_barrier() {
+  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier"
+               :
+               : "i"(ZTA_SAFE_WAITS ? 0 : N)
+               : "memory");
+}
+
+// MFMA chains with arch-VGPR accumulators, for kernels whose resident
+// accumulators already fill the accumulation-register file: the compiler
+// gives every builtin MFMA an AGPR destination, so a transient S / dP / dQ
+// tile issued through the builtin would evict resident tiles around each
+// use. Hazards the compiler cannot pad inside an asm statement are padded
+// here: `s_nop 1` covers a just-written operand, the closing `s_nop 11` the
+// 8-pass result -> any reader (each statement may be followed by compiler
+// copies of the accumulator). Accumulate chains need no pad in between.
+//
+// Two k-steps of S += A_q B_k and dP += A_do B_v (C[i=q][j=key]); FIRST
+// starts both chains from zero.
+template <bool FIRST>
+ZTA_DEV void mfma_sdp2(f32x16& s, f32x16& dp, const bf16x8* qa, const bf16x8* da,
+                       const bf16x8* kb, const bf16x8* vb) {
+  if (FIRST) {
+    asm("s_nop 1\n\t"
+        "v_mfma_f32_32x32x16_bf16 %0, %2, %6, 0\n\t"
+        "v_mfma_f32_32x32x16_bf16 %1, %4, %8, 0\n\t"
+        "v_mfma_f32_32x32x16_bf16 %0, %3, %7, %0\n\t"
+        "v_mfma_f32_32x32x16_bf16 %1, %5, %9, %1\n\t"
+        "s_nop 11"
+        : "=&v"(s), "=&v"(dp)
+        : "v"(qa[0]), "v"(qa[1]), "v"(da[0]), "v"(da[1]), "v"(kb[0]), "v"(kb[1]),
+          "v"(vb[0]), "v"(vb[1]));
+  } else {
+    asm("s_nop 1\n\t"
+        "v_mfma_f32_32x32x16_bf16 %0, %2, %6, %0\n\t"
+        "v_mfma_f32_32x32x16_bf16 %1, %4, %8, %1\n\t"
+        "v_mfma_f32_32x32x16_bf16 %0, %3, %7, %0\n\t"
+        "v_mfma_f32_32x32x16_bf16 %1, %5, %9, %1\n\t"
+        "s_nop 11"
+        : "+v"(s), "+v"(dp)
+        : "v"(qa[0]), "v"(qa[1]), "v"(da[0]), "v"(da[1]), "v"(kb[0]), "v"(kb[1]),
+          "v"(vb[0]), "v"(vb[1]));
+  }
+}
+
+// acc += x.a y.a + x.b y.b for a quad already drained with tr_quad_wait.
+ZTA_DEV void mfma_quad_acc(f32x16& acc, const TrQuad& t) {
+  asm("s_nop 1\n\t"
+      "v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0\n\t"
+      "v_mfma_f32_32x32x16_bf16 %0, %3, %4, %0\n\t"
+      "s_nop 11"
+      : "+v"(acc)
+      : "v"(t.x.a), "v"(t.y.a), "v"(t.x.b), "v"(t.y.b));
+}
+
+// Workgroup barrier that orders LDS traffic only: drains this wave's DS ops
+// (lgkmcnt) but NOT vmcnt, so global atomics issued before it stay in
+// flight. The "memory" clobber keeps plain LDS stores above it and, being a
+// volatile asm, every later transpose read stays below it.
+ZTA_DEV void lds_barrier() {
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
 template <int N>
@@ -275,15 +382,15 @@ ZTA_DEV void c_to_a_frags(const float* x, bf16x8* pa) {
 // to the source side). Rows beyond T are clamped to row T-1: the data is
 // finite real-tensor content and every consumer masks those rows to p = 0.
 // NWAVES = threads/64; chunk k (4 rows) is staged by wave k % NWAVES.
-template <int D, int NWAVES>
+// ROWS (multiple of 4) stages a shorter tile, e.g. one 32-row slice.
+template <int D, int NWAVES, int ROWS = TB>
 ZTA_DEV void glds_stage(const uint16_t* g, long base, int rs, int row0, int T,
-                        uint16_t* lds) {
+                        uint16_t* lds, int l = threadIdx.x & 63) {
   const int wave = (threadIdx.x >> 6);
-  const int l = threadIdx.x & 63;
   const int s = l & 15;        // 16 B slot within the 256 B image row
   const int rsub = l >> 4;     // row within the chunk's 4 rows
 #pragma unroll
-  for (int k = wave; k < 16; k += NWAVES) {
+  for (int k = wave; k < ROWS / 4; k += NWAVES) {
     const int row = 4 * k + rsub;
     int c8 = 8 * (s ^ (row & 7));  // swizzled source column block
     if (D < 128 && c8 >= D) c8 = 0;  // slot never read for cols >= D
@@ -292,6 +399,17 @@ ZTA_DEV void glds_stage(const uint16_t* g, long base, int rs, int row0, int T,
         (const __attribute__((address_space(1))) void*)&g[base + (long)rg * rs + c8],
         (__attribute__((address_space(3))) void*)(lds + (long)k * 512), 16, 0, 0);
   }
+}
+
+// LDS-DMA of the per-row f32 statistics of a 32-row slice, one wave
+// instruction (4 B per lane): dst[0..31] = a[rowbase + q], dst[32..63] =
+// b[rowbase + q] for q = q0..q0+31, rows past T clamped to T-1.
+ZTA_DEV void glds_stats32(const float* a, const float* b, long rowbase, int q0, int T,
+                          float* dst, int l = threadIdx.x & 63) {
+  const float* src = (l < 32 ? a : b) + rowbase + min(q0 + (l & 31), T - 1);
+  __builtin_amdgcn_global_load_lds(
+      (const __attribute__((address_space(1))) void*)src,
+      (__attribute__((address_space(3))) void*)dst, 4, 0, 0);
 }
 
 // T14 tile staging of a 64-row x D-col bf16 tile into a 256 B-stride

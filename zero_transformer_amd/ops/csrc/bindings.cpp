@@ -26,7 +26,7 @@ std::vector<at::Tensor> attn_fwd(at::Tensor qkv, at::Tensor slopes, int64_t H,
                                  double p_drop, int64_t seed);
 std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor qkv, at::Tensor slopes,
                                  at::Tensor o, at::Tensor lse, int64_t H,
-                                 double p_drop, int64_t seed);
+                                 double p_drop, int64_t seed, int64_t fused);
 at::Tensor gemm_gelu(at::Tensor x, at::Tensor w);
 at::Tensor gemv(at::Tensor x, at::Tensor w);
 
@@ -44,7 +44,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("residual_dropout_bwd", &residual_dropout_bwd, "fused x + dropout(h) bwd (gfx950)");
   m.def("attn_decode", &attn_decode, "single-token KV-cache ALiBi attention (gfx950)");
   m.def("attn_fwd", &attn_fwd, "fused causal ALiBi flash attention fwd (gfx950 MFMA)");
-  m.def("attn_bwd", &attn_bwd, "fused causal ALiBi flash attention bwd (gfx950 MFMA)");
+  // fused: -1 = process default (ZTA_BWD_FUSED), 0 = two-kernel dq + dkdv,
+  // 1 = single fused kernel (head_dim 128; other dims take the two-kernel path)
+  m.def("attn_bwd", &attn_bwd, "fused causal ALiBi flash attention bwd (gfx950 MFMA)",
+        py::arg("dout"), py::arg("qkv"), py::arg("slopes"), py::arg("o"),
+        py::arg("lse"), py::arg("H"), py::arg("p_drop"), py::arg("seed"),
+        py::arg("fused") = -1);
   m.def("gemm_gelu", &gemm_gelu,
         "hipBLASLt x@w^T with fused GELU epilogue (no-grad path)");
   m.def("gemv", &gemv, "weight-streaming decode GEMV x@w^T (gfx950)");
