@@ -484,7 +484,8 @@ def adamw_step(
 
     Reference semantics (optax chain, main_zero.py:160-168): grad * grad_scale
     (the 1/accum of xmap_train_functions.py:81), element-wise clip to
-    +-clip_value, Adam moments with bias correction, decoupled weight decay
+    +-clip_value (clip_value = 0 disables clipping, on GPU and CPU alike),
+    Adam moments with bias correction, decoupled weight decay
     (0 for no-decay buckets), -lr scale. When `param_bf16_out` is given the
     updated fp32 params are also written as bf16 (the working copy that gets
     all-gathered).

@@ -20,7 +20,9 @@ ZTA_DEV void adamw_elem(float& pi, uint16_t* pb, float& mi_io, float& vi_io,
                         float wd, float clip, float gscale, float inv_bc1,
                         float inv_bc2) {
   float gi = to_f32(gv) * gscale;
-  gi = fminf(fmaxf(gi, -clip), clip);
+  // clip == 0 turns clipping off (as reference.adamw_update), it does not
+  // clamp every gradient to 0
+  if (clip != 0.f) gi = fminf(fmaxf(gi, -clip), clip);
   float mi = beta1 * mi_io + (1.f - beta1) * gi;
   float vi = beta2 * vi_io + (1.f - beta2) * gi * gi;
   mi_io = mi;

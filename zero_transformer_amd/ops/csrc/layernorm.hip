@@ -18,24 +18,33 @@
 namespace {
 
 // ---------------------------------------------------------------------------
-// Fast path: bf16, C % 8 == 0, block = C/8 threads (<= 1024). The whole row
-// lives in one s16x8 per thread.
+// Fast path: bf16, C % 8 == 0, one s16x8 per thread (C/8 <= 1024). The whole
+// row lives in registers. The block is C/8 rounded up to whole waves: the
+// reductions (block_reduce_sum, the joint reduce in ln_bwd_vec) count
+// blockDim.x / WAVE waves and run a 64-wide butterfly, so a trailing partial
+// wave would be dropped from every row statistic. PARTIAL instances carry the
+// extra lanes (t * 8 >= C): they load nothing, contribute 0 and store nothing.
+// PARTIAL = false (C % 512 == 0) compiles to the unpredicated kernel.
 // ---------------------------------------------------------------------------
+template <bool PARTIAL>
 __global__ __launch_bounds__(1024) void ln_fwd_vec(
     const uint16_t* __restrict__ x, const uint16_t* __restrict__ w,
     uint16_t* __restrict__ y, float* __restrict__ mean_out,
     float* __restrict__ rstd_out, long rows, int C, float eps) {
   __shared__ float scratch[16];
   const int t = threadIdx.x;
+  const bool live = !PARTIAL || t * 8 < C;
   float wv[8];
   {
-    s16x8 w8 = *reinterpret_cast<const s16x8*>(&w[t * 8]);
+    s16x8 w8 = {};
+    if (live) w8 = *reinterpret_cast<const s16x8*>(&w[t * 8]);
 #pragma unroll
     for (int e = 0; e < 8; ++e) wv[e] = bf16_to_f32((uint16_t)w8[e]);
   }
   const float invC = 1.0f / (float)C;
   for (long row = blockIdx.x; row < rows; row += gridDim.x) {
-    s16x8 x8 = *reinterpret_cast<const s16x8*>(&x[row * C + t * 8]);
+    s16x8 x8 = {};
+    if (live) x8 = *reinterpret_cast<const s16x8*>(&x[row * C + t * 8]);
     float xv[8];
     float sum = 0.f, sumsq = 0.f;
 #pragma unroll
@@ -56,7 +65,7 @@ __global__ __launch_bounds__(1024) void ln_fwd_vec(
 #pragma unroll
     for (int e = 0; e < 8; ++e)
       y8[e] = (short)f32_to_bf16((xv[e] - mu) * rstd * wv[e]);
-    *reinterpret_cast<s16x8*>(&y[row * C + t * 8]) = y8;
+    if (live) *reinterpret_cast<s16x8*>(&y[row * C + t * 8]) = y8;
   }
 }
 
@@ -66,6 +75,7 @@ __global__ __launch_bounds__(1024) void ln_fwd_vec(
 // dw_part[block][C] (no atomics — an atomic tail at grid 2048 was 4.2M
 // atomicAdds onto 2048 words and dominated the kernel), reduced by
 // ln_dw_reduce. The two row statistics reduce together (one barrier set).
+template <bool PARTIAL>
 __global__ __launch_bounds__(1024) void ln_bwd_vec(
     const uint16_t* __restrict__ dy, const uint16_t* __restrict__ x,
     const uint16_t* __restrict__ w, const float* __restrict__ mean,
@@ -73,9 +83,11 @@ __global__ __launch_bounds__(1024) void ln_bwd_vec(
     float* __restrict__ dw_part, long rows, int C) {
   __shared__ float scratch[32];
   const int t = threadIdx.x;
+  const bool live = !PARTIAL || t * 8 < C;
   float wv[8], dw_acc[8];
   {
-    s16x8 w8 = *reinterpret_cast<const s16x8*>(&w[t * 8]);
+    s16x8 w8 = {};
+    if (live) w8 = *reinterpret_cast<const s16x8*>(&w[t * 8]);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       wv[e] = bf16_to_f32((uint16_t)w8[e]);
@@ -85,8 +97,11 @@ __global__ __launch_bounds__(1024) void ln_bwd_vec(
   const float invC = 1.0f / (float)C;
   const int lane = t & (WAVE - 1), wid = t / WAVE, nw = blockDim.x / WAVE;
   for (long row = blockIdx.x; row < rows; row += gridDim.x) {
-    s16x8 dy8 = *reinterpret_cast<const s16x8*>(&dy[row * C + t * 8]);
-    s16x8 x8 = *reinterpret_cast<const s16x8*>(&x[row * C + t * 8]);
+    s16x8 dy8 = {}, x8 = {};
+    if (live) {
+      dy8 = *reinterpret_cast<const s16x8*>(&dy[row * C + t * 8]);
+      x8 = *reinterpret_cast<const s16x8*>(&x[row * C + t * 8]);
+    }
     const float mu = mean[row], rs = rstd[row];
     float g[8], xh[8];
     float s1 = 0.f, s2 = 0.f;
@@ -123,8 +138,9 @@ __global__ __launch_bounds__(1024) void ln_bwd_vec(
 #pragma unroll
     for (int e = 0; e < 8; ++e)
       dx8[e] = (short)f32_to_bf16((g[e] - s1 - xh[e] * s2) * rs);
-    *reinterpret_cast<s16x8*>(&dx[row * C + t * 8]) = dx8;
+    if (live) *reinterpret_cast<s16x8*>(&dx[row * C + t * 8]) = dx8;
   }
+  if (!live) return;
   f32x4 p0 = {dw_acc[0], dw_acc[1], dw_acc[2], dw_acc[3]};
   f32x4 p1 = {dw_acc[4], dw_acc[5], dw_acc[6], dw_acc[7]};
   *reinterpret_cast<f32x4*>(&dw_part[(long)blockIdx.x * C + t * 8]) = p0;
@@ -223,7 +239,7 @@ __global__ void ln_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x,
 // pure launch/latency at decode's (B, 1, C) rows — 4 such pairs/layer were
 // ~0.45 ms of the 2.3 ms/token budget). fp16/bf16, one workgroup per row.
 // ---------------------------------------------------------------------------
-template <bool F16>
+template <bool F16, bool PARTIAL>
 __global__ __launch_bounds__(1024) void add_ln_vec(
     const uint16_t* __restrict__ x, const uint16_t* __restrict__ h,
     const uint16_t* __restrict__ w, uint16_t* __restrict__ y,
@@ -244,16 +260,21 @@ __global__ __launch_bounds__(1024) void add_ln_vec(
     }
     return f32_to_bf16(f);
   };
+  const bool live = !PARTIAL || t * 8 < C;
   float wv[8];
   {
-    s16x8 w8 = *reinterpret_cast<const s16x8*>(&w[t * 8]);
+    s16x8 w8 = {};
+    if (live) w8 = *reinterpret_cast<const s16x8*>(&w[t * 8]);
 #pragma unroll
     for (int e = 0; e < 8; ++e) wv[e] = cvt((uint16_t)w8[e]);
   }
   const float invC = 1.0f / (float)C;
   for (long row = blockIdx.x; row < rows; row += gridDim.x) {
-    s16x8 x8 = *reinterpret_cast<const s16x8*>(&x[row * C + t * 8]);
-    s16x8 h8 = *reinterpret_cast<const s16x8*>(&h[row * C + t * 8]);
+    s16x8 x8 = {}, h8 = {};
+    if (live) {
+      x8 = *reinterpret_cast<const s16x8*>(&x[row * C + t * 8]);
+      h8 = *reinterpret_cast<const s16x8*>(&h[row * C + t * 8]);
+    }
     float v[8];
     float sum = 0.f, sumsq = 0.f;
     s16x8 y8;
@@ -264,7 +285,7 @@ __global__ __launch_bounds__(1024) void add_ln_vec(
       sum += v[e];
       sumsq += v[e] * v[e];
     }
-    *reinterpret_cast<s16x8*>(&y[row * C + t * 8]) = y8;
+    if (live) *reinterpret_cast<s16x8*>(&y[row * C + t * 8]) = y8;
     sum = block_reduce_sum(sum, scratch);
     sumsq = block_reduce_sum(sumsq, scratch);
     const float mu = sum * invC;
@@ -272,9 +293,12 @@ __global__ __launch_bounds__(1024) void add_ln_vec(
     s16x8 l8;
 #pragma unroll
     for (int e = 0; e < 8; ++e) l8[e] = (short)enc((v[e] - mu) * rstd * wv[e]);
-    *reinterpret_cast<s16x8*>(&ln[row * C + t * 8]) = l8;
+    if (live) *reinterpret_cast<s16x8*>(&ln[row * C + t * 8]) = l8;
   }
 }
+
+// Vector-path block: one thread per 8 columns, rounded up to whole waves.
+inline int vec_block(int C) { return (C / 8 + WAVE - 1) / WAVE * WAVE; }
 
 }  // namespace
 
@@ -292,19 +316,23 @@ std::vector<at::Tensor> add_ln_fwd(at::Tensor x, at::Tensor h, at::Tensor w,
   auto y = at::empty_like(x);
   auto ln = at::empty_like(x);
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
-  const int block = C / 8;
+  const int block = vec_block(C);
+  const bool partial = block * 8 != C;
   const int grid = int(std::min<long>(rows, 4096));
+#define ZTA_ADD_LN(F16V, PARTIALV)                                                 \
+  hipLaunchKernelGGL((add_ln_vec<F16V, PARTIALV>), dim3(grid), dim3(block), 0,     \
+                     stream, (const uint16_t*)x.data_ptr(),                        \
+                     (const uint16_t*)h.data_ptr(), (const uint16_t*)w.data_ptr(), \
+                     (uint16_t*)y.data_ptr(), (uint16_t*)ln.data_ptr(), rows, C,   \
+                     (float)eps)
   if (x.scalar_type() == at::kHalf) {
-    hipLaunchKernelGGL((add_ln_vec<true>), dim3(grid), dim3(block), 0, stream,
-                       (const uint16_t*)x.data_ptr(), (const uint16_t*)h.data_ptr(),
-                       (const uint16_t*)w.data_ptr(), (uint16_t*)y.data_ptr(),
-                       (uint16_t*)ln.data_ptr(), rows, C, (float)eps);
+    if (partial) ZTA_ADD_LN(true, true);
+    else ZTA_ADD_LN(true, false);
   } else {
-    hipLaunchKernelGGL((add_ln_vec<false>), dim3(grid), dim3(block), 0, stream,
-                       (const uint16_t*)x.data_ptr(), (const uint16_t*)h.data_ptr(),
-                       (const uint16_t*)w.data_ptr(), (uint16_t*)y.data_ptr(),
-                       (uint16_t*)ln.data_ptr(), rows, C, (float)eps);
+    if (partial) ZTA_ADD_LN(false, true);
+    else ZTA_ADD_LN(false, false);
   }
+#undef ZTA_ADD_LN
   return {y, ln};
 }
 
@@ -320,12 +348,16 @@ std::vector<at::Tensor> layernorm_fwd(at::Tensor x, at::Tensor w, double eps) {
   const bool vec = x.scalar_type() == at::kBFloat16 && C % 8 == 0 && C / 8 >= 64 &&
                    C / 8 <= 1024;
   if (vec) {
-    const int block = C / 8;
+    const int block = vec_block(C);
     const int grid = int(std::min<long>(rows, 4096));
-    hipLaunchKernelGGL(ln_fwd_vec, dim3(grid), dim3(block), 0, stream,
-                       (const uint16_t*)x.data_ptr(), (const uint16_t*)w.data_ptr(),
-                       (uint16_t*)y.data_ptr(), mean.data_ptr<float>(),
-                       rstd.data_ptr<float>(), rows, C, (float)eps);
+#define ZTA_LN_FWD(PARTIALV)                                                      \
+  hipLaunchKernelGGL(ln_fwd_vec<PARTIALV>, dim3(grid), dim3(block), 0, stream,    \
+                     (const uint16_t*)x.data_ptr(), (const uint16_t*)w.data_ptr(), \
+                     (uint16_t*)y.data_ptr(), mean.data_ptr<float>(),             \
+                     rstd.data_ptr<float>(), rows, C, (float)eps)
+    if (block * 8 != C) ZTA_LN_FWD(true);
+    else ZTA_LN_FWD(false);
+#undef ZTA_LN_FWD
   } else if (x.scalar_type() == at::kBFloat16) {
     hipLaunchKernelGGL(ln_fwd_kernel<uint16_t>, dim3(int(std::min<long>(rows, 2048))),
                        dim3(256), 0, stream, (const uint16_t*)x.data_ptr(),
@@ -344,6 +376,11 @@ std::vector<at::Tensor> layernorm_fwd(at::Tensor x, at::Tensor w, double eps) {
 
 std::vector<at::Tensor> layernorm_bwd(at::Tensor dy, at::Tensor x, at::Tensor w,
                                       at::Tensor rstd, at::Tensor mean) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && dy.is_contiguous() &&
+              w.is_contiguous());
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kFloat,
+              "layernorm: unsupported dtype");
+  TORCH_CHECK(dy.scalar_type() == x.scalar_type() && w.scalar_type() == x.scalar_type());
   const int C = x.size(-1);
   const long rows = x.numel() / C;
   auto dx = at::empty_like(x);
@@ -352,24 +389,33 @@ std::vector<at::Tensor> layernorm_bwd(at::Tensor dy, at::Tensor x, at::Tensor w,
   const bool vec = x.scalar_type() == at::kBFloat16 && C % 8 == 0 && C / 8 >= 64 &&
                    C / 8 <= 1024;
   if (vec) {
-    const int block = C / 8;
+    const int block = vec_block(C);
     // 4096 blocks (16/CU): at 512 the kernel was occupancy-bound (each CU
     // held only 2 x 256-thread blocks walking 64 rows serially through
     // two barriers per row); 2048 measured 5.50 -> 4.05 ms/step at the
     // bench shape. dw_part grows to 32 MB at C=2048 — noise.
     const int grid = int(std::min<long>(rows, 4096));
     auto dw_part = at::empty({grid, C}, x.options().dtype(at::kFloat));
-    hipLaunchKernelGGL(ln_bwd_vec, dim3(grid), dim3(block), 0, stream,
-                       (const uint16_t*)dy.data_ptr(), (const uint16_t*)x.data_ptr(),
-                       (const uint16_t*)w.data_ptr(), mean.data_ptr<float>(),
-                       rstd.data_ptr<float>(), (uint16_t*)dx.data_ptr(),
-                       dw_part.data_ptr<float>(), rows, C);
+#define ZTA_LN_BWD(PARTIALV)                                                       \
+  hipLaunchKernelGGL(ln_bwd_vec<PARTIALV>, dim3(grid), dim3(block), 0, stream,     \
+                     (const uint16_t*)dy.data_ptr(), (const uint16_t*)x.data_ptr(), \
+                     (const uint16_t*)w.data_ptr(), mean.data_ptr<float>(),        \
+                     rstd.data_ptr<float>(), (uint16_t*)dx.data_ptr(),             \
+                     dw_part.data_ptr<float>(), rows, C)
+    if (block * 8 != C) ZTA_LN_BWD(true);
+    else ZTA_LN_BWD(false);
+#undef ZTA_LN_BWD
     hipLaunchKernelGGL(ln_dw_reduce, dim3((C + 255) / 256, 64), dim3(256), 0, stream,
                        dw_part.data_ptr<float>(), dw_f32.data_ptr<float>(), C, grid);
   } else {
     const int block = 256;
     const int grid = int(std::min<long>(rows, 1024));
-    const size_t smem = (C + 16) * sizeof(float);
+    const size_t smem = ((size_t)C + 16) * sizeof(float);
+    // the launch itself is unchecked: an over-limit LDS request would fail
+    // silently and hand back uninitialised dx
+    const size_t lds_max = at::cuda::getCurrentDeviceProperties()->sharedMemPerBlock;
+    TORCH_CHECK(smem <= lds_max, "layernorm_bwd: C=", C, " needs ", smem,
+                " bytes of LDS for the dw accumulator, device limit is ", lds_max);
     if (x.scalar_type() == at::kBFloat16) {
       hipLaunchKernelGGL(ln_bwd_kernel<uint16_t>, dim3(grid), dim3(block), smem, stream,
                          (const uint16_t*)dy.data_ptr(), (const uint16_t*)x.data_ptr(),
