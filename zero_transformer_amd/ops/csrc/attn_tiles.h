@@ -307,6 +307,37 @@ ZTA_DEV void tr_pair_issue(const uint16_t* lds, int k0, int j0, TrPair* out) {
       : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]));
 }
 
+// Base + immediate form of tr_pair_issue. For k0 a multiple of 8 and j0 a
+// multiple of 32 the swizzled address of tr_pair_issue splits into a
+// lane-constant term and a compile-time term (the XOR touches bits 4-5 from
+// the lane and bit 6 from the read index only), so the four reads share ONE
+// address register and carry their row / d-block in the DS offset field:
+//   addr = lds + tr_lane_off(l) + (K0 + 16*(i>>1) + 4*(i&1))*256
+//              + ((2*J0) ^ ((i&1) << 6)).
+ZTA_DEV int tr_lane_off(int l) {
+  const int q = (l >> 2) & 3;
+  return (8 * (l >> 5) + q) * 256 + ((2 * (l & 16) + 8 * (l & 3)) ^ (q << 4));
+}
+template <int K0, int J0>
+ZTA_DEV void tr_pair_issue_imm(int lane_base, TrPair* out) {
+  static_assert(K0 % 8 == 0 && J0 % 32 == 0, "offset split needs aligned k0/j0");
+  constexpr int O0 = (K0 + 0) * 256 + (2 * J0);
+  constexpr int O1 = (K0 + 4) * 256 + ((2 * J0) ^ 64);
+  constexpr int O2 = (K0 + 16) * 256 + (2 * J0);
+  constexpr int O3 = (K0 + 20) * 256 + ((2 * J0) ^ 64);
+  union U {
+    i32x2 d[4];
+    TrPair f;
+  }* u = (union U*)out;
+  asm volatile(
+      "ds_read_b64_tr_b16 %0, %4 offset:%5\n\t"
+      "ds_read_b64_tr_b16 %1, %4 offset:%6\n\t"
+      "ds_read_b64_tr_b16 %2, %4 offset:%7\n\t"
+      "ds_read_b64_tr_b16 %3, %4 offset:%8"
+      : "=&v"(u->d[0]), "=&v"(u->d[1]), "=&v"(u->d[2]), "=&v"(u->d[3])
+      : "v"(lane_base), "n"(O0), "n"(O1), "n"(O2), "n"(O3));
+}
+
 template <int N>
 ZTA_DEV void tr_pair_wait(TrPair* q) {
   union U {
