@@ -45,6 +45,29 @@ def _torch_flags():
     return includes, libdirs, abi
 
 
+def hipcc_compile_cmd() -> list:
+    """hipcc, the compile flags and the include paths, without sources, link
+    flags or output (shared with tools/kernel_isa.py)."""
+    includes, _, abi = _torch_flags()
+    cmd = [
+        os.environ.get("HIPCC", "hipcc"),
+        "--offload-arch=gfx950",
+        "-O3",
+        "-std=c++17",
+        "-fPIC",
+        f"-D_GLIBCXX_USE_CXX11_ABI={abi}",
+        "-DTORCH_EXTENSION_NAME=_zta_hip",
+        "-DTORCH_API_INCLUDE_EXTENSION_H",
+        "-DUSE_ROCM",
+        "-fno-gpu-rdc",
+        "-Wno-unused-result",
+    ]
+    cmd += os.environ.get("ZTA_HIPCC_EXTRA", "").split()
+    for i in includes:
+        cmd += ["-I", i]
+    return cmd
+
+
 def _src_hash() -> str:
     h = hashlib.sha256()
     h.update(os.environ.get("ZTA_HIPCC_EXTRA", "").encode())
@@ -64,27 +87,8 @@ def build(force: bool = False, verbose: bool = True) -> str:
     if not force and os.path.exists(OUT) and os.path.exists(STAMP):
         if open(STAMP).read().strip() == want:
             return OUT
-    includes, libdirs, abi = _torch_flags()
-    hipcc = os.environ.get("HIPCC", "hipcc")
-    cmd = [
-        hipcc,
-        "--offload-arch=gfx950",
-        "-O3",
-        "-std=c++17",
-        "-fPIC",
-        "-shared",
-        f"-D_GLIBCXX_USE_CXX11_ABI={abi}",
-        "-DTORCH_EXTENSION_NAME=_zta_hip",
-        "-DTORCH_API_INCLUDE_EXTENSION_H",
-        "-DUSE_ROCM",
-        "-fno-gpu-rdc",
-        "-Wno-unused-result",
-    ]
-    extra = os.environ.get("ZTA_HIPCC_EXTRA", "")
-    if extra:
-        cmd += extra.split()
-    for i in includes:
-        cmd += ["-I", i]
+    _, libdirs, _ = _torch_flags()
+    cmd = hipcc_compile_cmd() + ["-shared"]
     cmd += [os.path.join(CSRC, s) for s in SOURCES]
     for d in libdirs:
         cmd += ["-L", d, f"-Wl,-rpath,{d}"]

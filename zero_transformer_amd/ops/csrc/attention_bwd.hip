@@ -1,7 +1,9 @@
 // Flash attention backward for gfx950 (CDNA4 MFMA) with P recomputed from
 // the saved per-row LSE — no O(T^2) tensor is ever materialized (the
 // reference's autograd attention backward re-materializes the dense probs;
-// SURVEY.md §2.3 "Backward of all above"). Two schemes:
+// SURVEY.md §2.3 "Backward of all above"). Two schemes, three flash kernels
+// (flash_bwd_fused_kernel | flash_dq_kernel + flash_dkdv4_kernel), all after
+// the delta kernel:
 //
 // FUSED (head_dim 128, the default there): delta kernel, then ONE
 // key-stationary kernel (flash_bwd_fused_kernel) that computes S and dP
@@ -14,10 +16,11 @@
 // run; dK and dV are bitwise reproducible.
 //
 // TWO-KERNEL (all head dims; bitwise reproducible): the FA2-style dQ and
-// dKdV kernels below. ZTA_BWD_FUSED=0 selects it process-wide,
-// ZTA_BWD_FUSED=1 the fused scheme; the binding's trailing `fused` argument
-// (-1 default / 0 / 1) selects per call. Head dims other than 128 always
-// take the two-kernel path.
+// dKdV kernels below, which write disjoint columns of dqkv and run
+// concurrently, dQ on the caller's stream and dKdV on a side stream.
+// ZTA_BWD_FUSED=0 selects it process-wide, ZTA_BWD_FUSED=1 the fused scheme;
+// the binding's trailing `fused` argument (-1 default / 0 / 1) selects per
+// call. Head dims other than 128 always take the two-kernel path.
 //
 //   delta[b,h,i] = sum_d dO * O                  (delta kernel)
 //   dQ kernel : per 256-row Q block (8 waves x 32 rows), loop 64-key tiles:
@@ -28,8 +31,9 @@
 //       (v_cvt_pk_bf16_f32 + v_permlane32_swap, same transform as the fwd)
 //       and K^T B-fragments via ds_read_b64_tr_b16 hardware-transpose reads
 //       of the row-major XOR-swizzled K tile (no transposed staging copy).
-//   dKdV kernel: per 256-key KV block (8 waves x 32 keys, K/V resident in
-//       registers), loop 64-row Q tiles:
+//   dKdV kernel: per 128-key KV block (4 waves x 32 keys, one wave per SIMD
+//       with the whole register file: K/V resident in registers, no spills),
+//       loop 64-row Q tiles:
 //       S = Q K^T, dP = dO V^T       (C[i=q][j=key]: key is lane-resident),
 //       dV += P^T dO, dK += sc*(dS^T) Q  with P^T / dS^T A-fragments
 //       in-register and Q^T / dO^T B-fragments via tr-reads.
@@ -38,10 +42,7 @@
 // drop_bits32) with the forward's seed. All softmax math fp32. Tile staging
 // is direct LDS-DMA (global_load_lds_dwordx4, attn::glds_stage) into
 // double-buffered swizzled images: the prefetch for tile t+1 issues right
-// after tile t becomes visible, one barrier per tile. The default dKdV is
-// the 4-wave whole-register-file variant (flash_dkdv4_kernel, zero spills)
-// running concurrently with dQ on a side stream; the 8-wave kernels remain
-// selectable via ZTA_DKDV4=0 / ZTA_DQ4=1 for A/B.
+// after tile t becomes visible, one barrier per tile.
 
 #include "attn_tiles.h"
 #include "common.h"
@@ -55,15 +56,11 @@
 
 namespace {
 
-using attn::NW;
 using attn::RB;
 using attn::TB;
-using attn::Stage;
 using attn::c_to_a_frags;
 using attn::swz;
-using attn::tr_frag;
 
-constexpr float NEG_INF = -3.0e38f;
 // log2-domain softmax recompute: p = exp2(s*scale2 + slope2*(j-i) - lse2)
 // with scale2/slope2/lse2 pre-multiplied by log2(e) — raw v_exp_f32, no
 // hidden per-element multiply (matches the forward's folded softmax).
@@ -131,9 +128,8 @@ __global__ void delta_kernel_v8(const uint16_t* __restrict__ dout,
 }
 
 // ---------------------------------------------------------------------------
-// ---------------------------------------------------------------------------
 // dQ kernel: 8 waves x 32 q rows = 256-row Q block; loop 64-key KV tiles.
-// LDS: k_lds 64x[256B] swizzled | v_lds 64x[256B] swizzled   (32 KiB)
+// LDS: two buffers of k_lds 64x[256B] | v_lds 64x[256B], swizzled (64 KiB)
 // ---------------------------------------------------------------------------
 template <int D>
 __global__ __launch_bounds__(512, 2) void flash_dq_kernel(
@@ -146,12 +142,7 @@ __global__ __launch_bounds__(512, 2) void flash_dq_kernel(
   uint16_t* lds0 = (uint16_t*)smem;
 
   const int bh = blockIdx.x;  // grid: (BH, tiles) for per-CU load balance
-  const int h = bh % H;
-  const int QS = 3 * C;
-  const long base = (long)(bh / H) * T * QS + h * D;   // q plane of qkv
-  const long kbase = base + C;
-  const long vbase = base + 2 * C;
-  const long dobase = (long)(bh / H) * T * C + h * D;  // dout plane
+  const auto [h, QS, base, kbase, vbase, dobase] = attn::planes<D>(bh, H, T, C);
   const int q0 = blockIdx.y * RB;
   const int wave = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
@@ -161,12 +152,15 @@ __global__ __launch_bounds__(512, 2) void flash_dq_kernel(
   const float slope = slopes[h];
   const float scale2 = scale * LOG2E;
   const float slope2 = slope * LOG2E;
-  const uint32_t thr = (uint32_t)(p_drop * 256.0f + 0.5f);
-  const float inv_keep = thr ? 256.0f / (256.0f - (float)thr) : 1.0f;
+  const uint32_t thr = attn::drop_thr(p_drop);
+  const float inv_keep = attn::drop_inv_keep(thr);
 
   constexpr int KS = D / 16;
   constexpr int DB = D / 32;
 
+  // Literal on purpose, like the epilogue store and their twins in
+  // flash_dkdv4_kernel: shared helpers for either changed both kernels'
+  // instruction schedules at every head dim (tools/kernel_isa.py).
   bf16x8 q_frag[KS], do_frag[KS];
   {
     const bool ok = qi < T;
@@ -248,7 +242,7 @@ __global__ __launch_bounds__(512, 2) void flash_dq_kernel(
       } else {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int kj = kt32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+          const int kj = kt32 + attn::crow(r, hi);
           float p = 0.f;
           if (!(kj > qi || kj >= T || qi >= T))
             p = exp2f(s_acc[r] * scale2 + slope2 * (float)(kj - qi) - lse2_q);
@@ -279,7 +273,7 @@ __global__ __launch_bounds__(512, 2) void flash_dq_kernel(
   // epilogue: dQ rows crow(r,hi)
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int row = (r & 3) + 8 * (r >> 2) + 4 * hi;
+    const int row = attn::crow(r, hi);
     const int qr = qw + row;
     if (qr >= T) continue;
 #pragma unroll
@@ -289,337 +283,27 @@ __global__ __launch_bounds__(512, 2) void flash_dq_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// dKdV kernel: 8 waves x 32 keys = 256-key block, K/V resident; loop 64-row
-// Q tiles. LDS: q_lds 64x[256B] swz | do_lds 64x[256B] swz | lse/delta 64 f32
+// dKdV kernel: 4 waves x 32 keys = 128-key block; loop 64-row Q tiles.
+// 256 threads, ONE wave per SIMD, whole register file per wave (no
+// 2-waves/SIMD cap) — K/V resident AND no spills, at the cost of losing the
+// partner wave's latency hiding. The 8-wave form it replaced spilled at head
+// dims 96 and 128 (profiles/PERF.md).
 // ---------------------------------------------------------------------------
-template <int D>
-__global__ __launch_bounds__(512, 2) void flash_dkdv_kernel(
-    const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ dout,
-    const float* __restrict__ lse, const float* __restrict__ delta,
-    const float* __restrict__ slopes, uint16_t* __restrict__ dqkv, int H, int T,
-    int C, float scale, float p_drop, uint32_t seed) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  uint16_t* q_lds = (uint16_t*)smem;
-  uint16_t* do_lds = q_lds + TB * 128;
-  float* lse_s = (float*)(do_lds + TB * 128);
-  float* delta_s = lse_s + TB;
+constexpr int RB4 = 128;  // 4 waves x 32 keys
 
-  const int bh = blockIdx.x;  // grid: (BH, tiles) for per-CU load balance
-  const int h = bh % H;
-  const int QS = 3 * C;
-  const long base = (long)(bh / H) * T * QS + h * D;   // q plane of qkv
-  const long kbase = base + C;
-  const long vbase = base + 2 * C;
-  const long dobase = (long)(bh / H) * T * C + h * D;
-  const int k0 = blockIdx.y * RB;
-  const int wave = threadIdx.x >> 6;
-  const int lane = threadIdx.x & 63;
-  const int li = lane & 31, hi = lane >> 5;
-  const int kw = k0 + wave * 32;  // this wave's first key
-  const int kj = kw + li;         // this lane's key column
-  const float slope = slopes[h];
-  const float scale2 = scale * LOG2E;
-  const float slope2 = slope * LOG2E;
-  const uint32_t thr = (uint32_t)(p_drop * 256.0f + 0.5f);
-  const float inv_keep = thr ? 256.0f / (256.0f - (float)thr) : 1.0f;
-
-  constexpr int KS = D / 16;
-  constexpr int DB = D / 32;
-
-  bf16x8 k_frag[KS], v_frag[KS];
-  {
-    const bool ok = kj < T;
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      if (ok) {
-        k_frag[s] = *reinterpret_cast<const bf16x8*>(&qkv[kbase + (long)kj * QS + s * 16 + 8 * hi]);
-        v_frag[s] = *reinterpret_cast<const bf16x8*>(&qkv[vbase + (long)kj * QS + s * 16 + 8 * hi]);
-      } else {
-        k_frag[s] = bf16x8{};
-        v_frag[s] = bf16x8{};
-      }
-    }
-  }
-
-  f32x16 dk_acc[DB], dv_acc[DB];
-#pragma unroll
-  for (int d = 0; d < DB; ++d) {
-    dk_acc[d] = f32x16{};
-    dv_acc[d] = f32x16{};
-  }
-
-  if (__builtin_amdgcn_readfirstlane(threadIdx.x) >= 256)
-    __builtin_amdgcn_s_setprio(1);  // static priority for the younger half (T5)
-
-  Stage<D> sq, sdo;
-  float lse_reg = 0.f, delta_reg = 0.f;
-  const int t512 = threadIdx.x;
-  auto load_stats = [&](int qt) {
-    if (t512 < TB) {
-      const int qg = qt + t512;
-      lse_reg = (qg < T ? lse[(long)bh * T + qg] : 0.f) * LOG2E;
-      delta_reg = qg < T ? delta[(long)bh * T + qg] : 0.f;
-    }
-  };
-
-  sq.load(qkv, base, QS, k0, T);
-  sdo.load(dout, dobase, C, k0, T);
-  load_stats(k0);
-  for (int qt = k0; qt < T; qt += TB) {
-    __syncthreads();
-    sq.store(q_lds);
-    sdo.store(do_lds);
-    if (t512 < TB) {
-      lse_s[t512] = lse_reg;
-      delta_s[t512] = delta_reg;
-    }
-    __syncthreads();
-    attn::lds_acquire();
-#ifndef ZTA_DKDV_NO_STAGE  // perf ablation: expose staging cost
-    if (qt + TB < T) {
-      sq.load(qkv, base, QS, qt + TB, T);
-      sdo.load(dout, dobase, C, qt + TB, T);
-      load_stats(qt + TB);
-    }
-#endif
-
-#pragma unroll
-    for (int sub = 0; sub < 2; ++sub) {
-      const int q32 = qt + sub * 32;
-      if (q32 + 31 < kw || q32 >= T) continue;  // q < key: fully masked
-
-      // S = Q K^T ; dP = dO V^T   (C[i=q][j=key], key = lane's column)
-      f32x16 s_acc{}, dp_acc{};
-#pragma unroll
-      for (int s = 0; s < KS; ++s) {
-        const int kk = s * 16 + 8 * hi;
-        const int qrow = sub * 32 + li;
-        bf16x8 qa = *reinterpret_cast<const bf16x8*>((char*)q_lds + swz(qrow, qrow * 256 + kk * 2));
-        bf16x8 da = *reinterpret_cast<const bf16x8*>((char*)do_lds + swz(qrow, qrow * 256 + kk * 2));
-        s_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa, k_frag[s], s_acc, 0, 0, 0);
-        dp_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da, v_frag[s], dp_acc, 0, 0, 0);
-      }
-
-      // P^T (for dV) and dS^T (for dK) per register; q = q32 + crow(r,hi)
-      float p_pv[16], ds[16];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = (r & 3) + 8 * (r >> 2) + 4 * hi;
-        const int qi = q32 + row;
-        const float lq = lse_s[sub * 32 + row];
-        const float dq_ = delta_s[sub * 32 + row];
-        float p = 0.f;
-        if (!(kj > qi || kj >= T || qi >= T))
-          p = exp2f(s_acc[r] * scale2 + slope2 * (float)(kj - qi) - lq);
-        float dp = dp_acc[r];
-        float ppv = p;
-        if (thr) {
-          const uint32_t bits = drop_bits32(seed, bh * T + qi, kj >> 2);
-          const bool keep = ((bits >> (8 * (kj & 3))) & 0xffu) >= thr;
-          dp = keep ? dp * inv_keep : 0.f;
-          ppv = keep ? p * inv_keep : 0.f;
-        }
-        p_pv[r] = ppv;
-        ds[r] = scale * p * (dp - dq_);
-      }
-
-      bf16x8 pa[2], dsa[2];
-      c_to_a_frags(p_pv, pa);  // A[i=key][k=q]
-      c_to_a_frags(ds, dsa);
-
-      // dV += P^T dO ; dK += dS^T Q : B[k=q][j=d] via tr-reads (all eight
-      // transpose reads of a d-block in one asm, one lgkmcnt drain)
-#ifndef ZTA_DKDV_NO_ACCUM  // perf ablation: expose accumulation-loop cost
-#pragma unroll
-      for (int d = 0; d < DB; ++d) {
-        attn::TrQuad t = attn::tr_frag_quad(do_lds, q_lds, sub * 32, d * 32);
-        dv_acc[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[0], t.x.a, dv_acc[d], 0, 0, 0);
-        dv_acc[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[1], t.x.b, dv_acc[d], 0, 0, 0);
-        dk_acc[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dsa[0], t.y.a, dk_acc[d], 0, 0, 0);
-        dk_acc[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dsa[1], t.y.b, dk_acc[d], 0, 0, 0);
-      }
-#endif
-    }
-  }
-
-  // epilogue: dK/dV rows crow(r,hi)
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int row = (r & 3) + 8 * (r >> 2) + 4 * hi;
-    const int kr = kw + row;
-    if (kr >= T) continue;
-#pragma unroll
-    for (int d = 0; d < DB; ++d) {
-      dqkv[kbase + (long)kr * QS + d * 32 + li] = f32_to_bf16(dk_acc[d][r]);
-      dqkv[vbase + (long)kr * QS + d * 32 + li] = f32_to_bf16(dv_acc[d][r]);
-    }
-  }
-}
-
-// 4-wave variant of dQ (same rationale as flash_dkdv4_kernel: one wave per
-// SIMD with the whole register file — Q/dO row fragments resident, zero
-// spills). 128 q rows per block.
-template <int D>
-__global__ __launch_bounds__(256, 1) void flash_dq4_kernel(
-    const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ dout,
-    const float* __restrict__ lse, const float* __restrict__ delta,
-    const float* __restrict__ slopes, uint16_t* __restrict__ dqkv, int H, int T,
-    int C, float scale, float p_drop, uint32_t seed) {
-  constexpr int RB4 = 128;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  uint16_t* k_lds = (uint16_t*)smem;
-  uint16_t* v_lds = k_lds + TB * 128;
-
-  const int bh = blockIdx.x;
-  const int h = bh % H;
-  const int QS = 3 * C;
-  const long base = (long)(bh / H) * T * QS + h * D;
-  const long kbase = base + C;
-  const long vbase = base + 2 * C;
-  const long dobase = (long)(bh / H) * T * C + h * D;
-  const int q0 = blockIdx.y * RB4;
-  const int wave = threadIdx.x >> 6;
-  const int lane = threadIdx.x & 63;
-  const int li = lane & 31, hi = lane >> 5;
-  const int qw = q0 + wave * 32;
-  const int qi = qw + li;
-  const float slope = slopes[h];
-  const float scale2 = scale * LOG2E;
-  const float slope2 = slope * LOG2E;
-  const uint32_t thr = (uint32_t)(p_drop * 256.0f + 0.5f);
-  const float inv_keep = thr ? 256.0f / (256.0f - (float)thr) : 1.0f;
-
-  constexpr int KS = D / 16;
-  constexpr int DB = D / 32;
-
-  bf16x8 q_frag[KS], do_frag[KS];
-  {
-    const bool ok = qi < T;
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      if (ok) {
-        q_frag[s] = *reinterpret_cast<const bf16x8*>(&qkv[base + (long)qi * QS + s * 16 + 8 * hi]);
-        do_frag[s] = *reinterpret_cast<const bf16x8*>(&dout[dobase + (long)qi * C + s * 16 + 8 * hi]);
-      } else {
-        q_frag[s] = bf16x8{};
-        do_frag[s] = bf16x8{};
-      }
-    }
-  }
-  const float lse2_q = (qi < T ? lse[(long)bh * T + qi] : 0.f) * LOG2E;
-  const float delta_q = qi < T ? delta[(long)bh * T + qi] : 0.f;
-
-  f32x16 dq_acc[DB];
-#pragma unroll
-  for (int d = 0; d < DB; ++d) dq_acc[d] = f32x16{};
-
-  Stage<D, 256> sk, sv;
-  sk.load(qkv, kbase, QS, 0, T);
-  sv.load(qkv, vbase, QS, 0, T);
-  const int kv_end = min(T, q0 + RB4);
-  for (int kt = 0; kt < kv_end; kt += TB) {
-    __syncthreads();
-    sk.store(k_lds);
-    sv.store(v_lds);
-    __syncthreads();
-    attn::lds_acquire();
-    if (kt + TB < kv_end) {
-      sk.load(qkv, kbase, QS, kt + TB, T);
-      sv.load(qkv, vbase, QS, kt + TB, T);
-    }
-
-#pragma unroll
-    for (int sub = 0; sub < 2; ++sub) {
-      const int kt32 = kt + sub * 32;
-      if (kt32 > qw + 31 || kt32 >= T) continue;
-
-      f32x16 s_acc{}, dpt_acc{};
-#pragma unroll
-      for (int s = 0; s < KS; ++s) {
-        const int kk = s * 16 + 8 * hi;
-        const int krow = sub * 32 + li;
-        bf16x8 ka = *reinterpret_cast<const bf16x8*>((char*)k_lds + swz(krow, krow * 256 + kk * 2));
-        bf16x8 va = *reinterpret_cast<const bf16x8*>((char*)v_lds + swz(krow, krow * 256 + kk * 2));
-        s_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka, q_frag[s], s_acc, 0, 0, 0);
-        dpt_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va, do_frag[s], dpt_acc, 0, 0, 0);
-      }
-
-      float ds[16];
-      if (thr) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int kbase_g = kt32 + 8 * g + 4 * hi;
-          const uint32_t bits = drop_bits32(seed, bh * T + qi, kbase_g >> 2);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const int r = 4 * g + e;
-            const int kj = kbase_g + e;
-            const bool masked = kj > qi || kj >= T || qi >= T;
-            const float x = masked ? -3.0e38f
-                                   : s_acc[r] * scale2 + slope2 * (float)(kj - qi) - lse2_q;
-            const float p = exp2f(x);
-            const bool keep = ((bits >> (8 * e)) & 0xffu) >= thr;
-            const float dp = keep ? dpt_acc[r] * inv_keep : 0.f;
-            ds[r] = scale * p * (dp - delta_q);
-          }
-        }
-      } else {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int kj = kt32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-          const bool masked = kj > qi || kj >= T || qi >= T;
-          const float x = masked ? -3.0e38f
-                                 : s_acc[r] * scale2 + slope2 * (float)(kj - qi) - lse2_q;
-          ds[r] = scale * exp2f(x) * (dpt_acc[r] - delta_q);
-        }
-      }
-
-      bf16x8 dsa[2];
-      c_to_a_frags(ds, dsa);
-
-#pragma unroll
-      for (int d = 0; d < DB; ++d) {
-        attn::TrPair kp = attn::tr_frag_pair(k_lds, sub * 32, d * 32);
-        dq_acc[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dsa[0], kp.a, dq_acc[d], 0, 0, 0);
-        dq_acc[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dsa[1], kp.b, dq_acc[d], 0, 0, 0);
-      }
-    }
-  }
-
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int row = (r & 3) + 8 * (r >> 2) + 4 * hi;
-    const int qr = qw + row;
-    if (qr >= T) continue;
-#pragma unroll
-    for (int d = 0; d < DB; ++d)
-      dqkv[base + (long)qr * QS + d * 32 + li] = f32_to_bf16(dq_acc[d][r]);
-  }
-}
-
-// 4-wave variant of dKdV: 256 threads, ONE wave per SIMD, whole register
-// file per wave (no 2-waves/SIMD cap) — K/V resident AND no spills, at the
-// cost of losing the partner wave's latency hiding. A/B-selected against
-// the 8-wave kernel via ZTA_DKDV4=1 (see launch_bwd).
 template <int D>
 __global__ __launch_bounds__(256, 1) void flash_dkdv4_kernel(
     const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ dout,
     const float* __restrict__ lse, const float* __restrict__ delta,
     const float* __restrict__ slopes, uint16_t* __restrict__ dqkv, int H, int T,
     int C, float scale, float p_drop, uint32_t seed) {
-  constexpr int RB4 = 128;  // 4 waves x 32 keys
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // LDS-DMA double buffers [q0 | do0 | q1 | do1] + 2x (lse, delta) slices
   uint16_t* lds0 = (uint16_t*)smem;
   float* stats0 = (float*)(lds0 + 4 * TB * 128);
 
   const int bh = blockIdx.x;
-  const int h = bh % H;
-  const int QS = 3 * C;
-  const long base = (long)(bh / H) * T * QS + h * D;
-  const long kbase = base + C;
-  const long vbase = base + 2 * C;
-  const long dobase = (long)(bh / H) * T * C + h * D;
+  const auto [h, QS, base, kbase, vbase, dobase] = attn::planes<D>(bh, H, T, C);
   const int k0 = blockIdx.y * RB4;
   const int wave = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
@@ -629,13 +313,13 @@ __global__ __launch_bounds__(256, 1) void flash_dkdv4_kernel(
   const float slope = slopes[h];
   const float scale2 = scale * LOG2E;
   const float slope2 = slope * LOG2E;
-  const uint32_t thr = (uint32_t)(p_drop * 256.0f + 0.5f);
-  const float inv_keep = thr ? 256.0f / (256.0f - (float)thr) : 1.0f;
+  const uint32_t thr = attn::drop_thr(p_drop);
+  const float inv_keep = attn::drop_inv_keep(thr);
 
   constexpr int KS = D / 16;
   constexpr int DB = D / 32;
 
-  bf16x8 k_frag[KS], v_frag[KS];
+  bf16x8 k_frag[KS], v_frag[KS];  // literal loop: see flash_dq_kernel
   {
     const bool ok = kj < T;
 #pragma unroll
@@ -713,7 +397,7 @@ __global__ __launch_bounds__(256, 1) void flash_dkdv4_kernel(
       float p_pv[16], ds[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = (r & 3) + 8 * (r >> 2) + 4 * hi;
+        const int row = attn::crow(r, hi);
         const int qi = q32 + row;
         const float lq = lse_s[sub * 32 + row];
         const float dq_ = delta_s[sub * 32 + row];
@@ -759,7 +443,7 @@ __global__ __launch_bounds__(256, 1) void flash_dkdv4_kernel(
 
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int row = (r & 3) + 8 * (r >> 2) + 4 * hi;
+    const int row = attn::crow(r, hi);
     const int kr = kw + row;
     if (kr >= T) continue;
 #pragma unroll
@@ -813,12 +497,7 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_fused_kernel(
   float* stats0 = (float*)(ds0 + 2 * FKB * 32);  // two [lse 32 | delta 32]
 
   const int bh = blockIdx.x;  // grid: (BH, key blocks), heaviest block first
-  const int h = bh % H;
-  const int QS = 3 * C;
-  const long base = (long)(bh / H) * T * QS + h * D;
-  const long kbase = base + C;
-  const long vbase = base + 2 * C;
-  const long dobase = (long)(bh / H) * T * C + h * D;
+  const auto [h, QS, base, kbase, vbase, dobase] = attn::planes<D>(bh, H, T, C);
   const int k0 = blockIdx.y * FKB;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
@@ -827,8 +506,8 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_fused_kernel(
   const float slope = slopes[h];
   const float scale2 = scale * LOG2E;
   const float slope2 = slope * LOG2E;
-  const uint32_t thr = (uint32_t)(p_drop * 256.0f + 0.5f);
-  const float inv_keep = thr ? 256.0f / (256.0f - (float)thr) : 1.0f;
+  const uint32_t thr = attn::drop_thr(p_drop);
+  const float inv_keep = attn::drop_inv_keep(thr);
 
   constexpr int KS = D / 16;
   constexpr int DB = D / 32;
@@ -955,6 +634,10 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_fused_kernel(
           const int kshift = 8 * (kj & 3);
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
+            // attn::crow(r, hi), spelled out in this kernel (here and at the
+            // dQ atomics and the epilogue below): with the helper the same
+            // values come out of a different instruction schedule (at the
+            // two sums even 8049 -> 8077 instructions), which nobody has timed.
             const int row = (r & 3) + 8 * (r >> 2) + 4 * hi;
             const int qi = q32 + row;
             const float lq = lse_s[row] * LOG2E;  // log2 domain
@@ -1036,7 +719,7 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_fused_kernel(
     // one register = rows crow(r,0) and crow(r,1), 128 B each; left in flight
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int qr = q32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+      const int qr = q32 + (r & 3) + 8 * (r >> 2) + 4 * hi;  // literal crow: see softmax
       if (qr < T) unsafeAtomicAdd(dq_col + (long)qr * C + li, dq[r]);
     }
   }
@@ -1046,7 +729,7 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_fused_kernel(
   for (int g = 0; g < 2; ++g)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int kr = kw + 32 * g + (r & 3) + 8 * (r >> 2) + 4 * hi;
+      const int kr = kw + 32 * g + (r & 3) + 8 * (r >> 2) + 4 * hi;  // literal crow
       if (kr >= T) continue;
 #pragma unroll
       for (int d = 0; d < DB; ++d) {
@@ -1078,10 +761,12 @@ __global__ void dq_convert_kernel(const float* __restrict__ dq32,
   }
 }
 
-// dq and dkdv are independent (disjoint column ranges of dqkv) and both
-// stall-bound at one 512-thread block per CU — run them CONCURRENTLY on two
-// streams so their blocks co-reside (227 + 256 VGPR and 32 + 64.5 KB LDS
-// both fit one CU) and each fills the other's wait cycles.
+// Two-kernel path: dq and dkdv are independent (disjoint column ranges of
+// dqkv) and each is stall-bound on its own, so they run CONCURRENTLY, dq on
+// the caller's stream and dkdv on this side stream, forked and joined with
+// the two events below: each kernel's blocks fill CUs and wait cycles the
+// other leaves idle. (A 4-wave dQ beside the 4-wave dKdV measured slower than
+// this 8-wave dQ: profiles/PERF.md.)
 inline hipStream_t bwd_side_stream() {
   static hipStream_t s = [] {
     hipStream_t t;
@@ -1091,16 +776,12 @@ inline hipStream_t bwd_side_stream() {
   return s;
 }
 inline hipEvent_t bwd_event(int i) {
-  static hipEvent_t e[2] = {[] {
-                              hipEvent_t t;
-                              (void)hipEventCreateWithFlags(&t, hipEventDisableTiming);
-                              return t;
-                            }(),
-                            [] {
-                              hipEvent_t t;
-                              (void)hipEventCreateWithFlags(&t, hipEventDisableTiming);
-                              return t;
-                            }()};
+  auto make = [] {
+    hipEvent_t t;
+    (void)hipEventCreateWithFlags(&t, hipEventDisableTiming);
+    return t;
+  };
+  static hipEvent_t e[2] = {make(), make()};
   return e[i];
 }
 
@@ -1109,49 +790,21 @@ void launch_bwd(const at::Tensor& qkv, const at::Tensor& dout, const at::Tensor&
                 const at::Tensor& delta, const at::Tensor& slopes, at::Tensor& dqkv,
                 int B, int H, int T, int C, float scale, float p_drop,
                 uint32_t seed, hipStream_t stream) {
-  dim3 grid(B * H, (T + RB - 1) / RB);
+  auto launch = [&](auto kernel, int rows, int threads, size_t smem, hipStream_t s) {
+    hipLaunchKernelGGL(kernel, dim3(B * H, (T + rows - 1) / rows), dim3(threads), smem, s,
+                       (const uint16_t*)qkv.data_ptr(), (const uint16_t*)dout.data_ptr(),
+                       lse.data_ptr<float>(), delta.data_ptr<float>(),
+                       slopes.data_ptr<float>(), (uint16_t*)dqkv.data_ptr(), H, T, C,
+                       scale, p_drop, seed);
+  };
+  // two double-buffered 64-row tiles; dkdv adds the (lse, delta) slices
+  const size_t smem_dq = 4 * TB * 128 * sizeof(uint16_t);
+  const size_t smem_kv = smem_dq + 4 * TB * sizeof(float);
   hipStream_t side = bwd_side_stream();
   (void)hipEventRecord(bwd_event(0), stream);
   (void)hipStreamWaitEvent(side, bwd_event(0), 0);
-  const size_t smem_dq = 4 * TB * 128 * sizeof(uint16_t);  // 2 tensors x 2 buffers
-  const size_t smem_dq4 = 2 * TB * 128 * sizeof(uint16_t);
-  static const bool dq4 = [] {
-    const char* e = getenv("ZTA_DQ4");
-    return e && e[0] == '1';  // default OFF: measured slower than the 8-wave
-                              // dq when concurrent with the 4-wave dKdV
-  }();
-  if (dq4) {
-    dim3 gridq(B * H, (T + 127) / 128);
-    hipLaunchKernelGGL(flash_dq4_kernel<D>, gridq, dim3(256), smem_dq4, stream,
-                       (const uint16_t*)qkv.data_ptr(), (const uint16_t*)dout.data_ptr(),
-                       lse.data_ptr<float>(), delta.data_ptr<float>(),
-                       slopes.data_ptr<float>(), (uint16_t*)dqkv.data_ptr(), H, T, C,
-                       scale, p_drop, seed);
-  } else
-  hipLaunchKernelGGL(flash_dq_kernel<D>, grid, dim3(512), smem_dq, stream,
-                     (const uint16_t*)qkv.data_ptr(), (const uint16_t*)dout.data_ptr(),
-                     lse.data_ptr<float>(), delta.data_ptr<float>(),
-                     slopes.data_ptr<float>(), (uint16_t*)dqkv.data_ptr(), H, T, C,
-                     scale, p_drop, seed);
-  const size_t smem_kv = 2 * TB * 128 * sizeof(uint16_t) + 2 * TB * sizeof(float);
-  const size_t smem_kv4 = 4 * TB * 128 * sizeof(uint16_t) + 4 * TB * sizeof(float);
-  static const bool use4 = [] {
-    const char* e = getenv("ZTA_DKDV4");
-    return !(e && e[0] == '0');  // default ON (zero spills beat 2 waves/SIMD)
-  }();
-  if (use4) {
-    dim3 grid4(B * H, (T + 127) / 128);
-    hipLaunchKernelGGL(flash_dkdv4_kernel<D>, grid4, dim3(256), smem_kv4, side,
-                       (const uint16_t*)qkv.data_ptr(), (const uint16_t*)dout.data_ptr(),
-                       lse.data_ptr<float>(), delta.data_ptr<float>(),
-                       slopes.data_ptr<float>(), (uint16_t*)dqkv.data_ptr(), H, T, C,
-                       scale, p_drop, seed);
-  } else
-  hipLaunchKernelGGL(flash_dkdv_kernel<D>, grid, dim3(512), smem_kv, side,
-                     (const uint16_t*)qkv.data_ptr(), (const uint16_t*)dout.data_ptr(),
-                     lse.data_ptr<float>(), delta.data_ptr<float>(),
-                     slopes.data_ptr<float>(), (uint16_t*)dqkv.data_ptr(), H, T, C,
-                     scale, p_drop, seed);
+  launch(flash_dq_kernel<D>, RB, 512, smem_dq, stream);
+  launch(flash_dkdv4_kernel<D>, RB4, 256, smem_kv, side);
   (void)hipEventRecord(bwd_event(1), side);
   (void)hipStreamWaitEvent(stream, bwd_event(1), 0);
 }
@@ -1232,12 +885,10 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor qkv, at::Tensor slo
                      (float)p_drop, (uint32_t)seed, stream);
     return {dqkv};
   }
-  switch (D) {
-    case 32: launch_bwd<32>(qkv, dout, lse, delta, sl, dqkv, B, H, T, C, scale, (float)p_drop, (uint32_t)seed, stream); break;
-    case 64: launch_bwd<64>(qkv, dout, lse, delta, sl, dqkv, B, H, T, C, scale, (float)p_drop, (uint32_t)seed, stream); break;
-    case 96: launch_bwd<96>(qkv, dout, lse, delta, sl, dqkv, B, H, T, C, scale, (float)p_drop, (uint32_t)seed, stream); break;
-    case 128: launch_bwd<128>(qkv, dout, lse, delta, sl, dqkv, B, H, T, C, scale, (float)p_drop, (uint32_t)seed, stream); break;
-    default: TORCH_CHECK(false, "attn_bwd: head_dim must be 32/64/96/128, got ", D);
-  }
+  const bool ok = attn::with_head_dim(D, [&](auto d) {
+    launch_bwd<decltype(d)::value>(qkv, dout, lse, delta, sl, dqkv, B, H, T, C, scale,
+                                   (float)p_drop, (uint32_t)seed, stream);
+  });
+  TORCH_CHECK(ok, "attn_bwd: head_dim must be 32/64/96/128, got ", D);
   return {dqkv};
 }

@@ -83,9 +83,7 @@ namespace {
 using attn::NW;
 using attn::RB;
 using attn::TB;
-using attn::Stage;
 using attn::swz;
-using attn::tr_frag;
 
 constexpr float NEG_INF = -3.0e38f;
 
@@ -104,12 +102,7 @@ __global__ __launch_bounds__(NT, MINW) void flash_fwd_kernel(
 
   const int bh = blockIdx.x;  // grid: (BH, tiles) — consecutive blocks share the
   // tile index so per-CU work is balanced across the causal triangle
-  const int h = bh % H;
-  const int QS = 3 * C;  // qkv row stride (elements)
-  const long base = (long)(bh / H) * T * QS + h * D;   // q plane
-  const long kbase = base + C;
-  const long vbase = base + 2 * C;
-  const long obase = (long)(bh / H) * T * C + h * D;   // o plane
+  const auto [h, QS, base, kbase, vbase, obase] = attn::planes<D>(bh, H, T, C);
   constexpr int RBX = NT / 2;  // NT=512: 256 q rows; NT=256: 128 q rows
   const int q0 = blockIdx.y * RBX;
   const int wave = threadIdx.x >> 6;
@@ -125,8 +118,8 @@ __global__ __launch_bounds__(NT, MINW) void flash_fwd_kernel(
   constexpr float DEFER_THR = 11.5f;  // ~8 nats in log2 bits
   const float scale2 = scale * LOG2E;
   const float slope2 = slope * LOG2E;
-  const uint32_t drop_thr = (uint32_t)(p_drop * 256.0f + 0.5f);
-  const float inv_keep = drop_thr ? 256.0f / (256.0f - (float)drop_thr) : 1.0f;
+  const uint32_t drop_thr = attn::drop_thr(p_drop);
+  const float inv_keep = attn::drop_inv_keep(drop_thr);
 
   constexpr int KS = D / 16;
   constexpr int DB = D / 32;
@@ -193,7 +186,7 @@ __global__ __launch_bounds__(NT, MINW) void flash_fwd_kernel(
       float tile_max = NEG_INF;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int kj = kt32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+        const int kj = kt32 + attn::crow(r, hi);
         float x = s_acc[r] * scale2 + slope2 * (float)(kj - qi);
         if (kj > qi || kj >= T || qi >= T) x = NEG_INF;
         sv_[r] = x;
@@ -241,7 +234,7 @@ __global__ __launch_bounds__(NT, MINW) void flash_fwd_kernel(
       if (!__all(alpha == 1.f)) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const float ar = __shfl(alpha, (r & 3) + 8 * (r >> 2) + 4 * hi, 64);
+          const float ar = __shfl(alpha, attn::crow(r, hi), 64);
 #pragma unroll
           for (int d = 0; d < DB; ++d) o_acc[d][r] *= ar;
         }
@@ -276,7 +269,7 @@ __global__ __launch_bounds__(NT, MINW) void flash_fwd_kernel(
     lse[(long)bh * T + qi] = l_run > 0.f ? m_run * LN2 + __logf(l_run) : NEG_INF;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int row = (r & 3) + 8 * (r >> 2) + 4 * hi;
+    const int row = attn::crow(r, hi);
     const int qr = qw + row;
     if (qr >= T) continue;
     const float il = __shfl(inv_l, row, 64);
@@ -345,12 +338,7 @@ __global__ __launch_bounds__(512, 2) void flash_fwd_v2_kernel(
   uint16_t* lds0 = (uint16_t*)smem;  // [k0 | v0 | k1 | v1], 16 KiB each
 
   const int bh = blockIdx.x;
-  const int h = bh % H;
-  const int QS = 3 * C;
-  const long base = (long)(bh / H) * T * QS + h * D;
-  const long kbase = base + C;
-  const long vbase = base + 2 * C;
-  const long obase = (long)(bh / H) * T * C + h * D;
+  const auto [h, QS, base, kbase, vbase, obase] = attn::planes<D>(bh, H, T, C);
   const int q0 = blockIdx.y * RB;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
@@ -367,7 +355,7 @@ __global__ __launch_bounds__(512, 2) void flash_fwd_v2_kernel(
   constexpr float DEFER_THR = 11.5f;  // ~8 nats in log2 bits
   const float scale2 = scale * LOG2E;
   const float slope2 = slopes[h] * LOG2E;
-  const uint32_t drop_thr = (uint32_t)(p_drop * 256.0f + 0.5f);
+  const uint32_t drop_thr = attn::drop_thr(p_drop);
 
   constexpr int KS = D / 16;
   constexpr int DB = D / 32;
@@ -490,7 +478,7 @@ __global__ __launch_bounds__(512, 2) void flash_fwd_v2_kernel(
       l_half *= alpha;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const float ar = __shfl(alpha, (r & 3) + 8 * (r >> 2) + 4 * hi, 64);
+        const float ar = __shfl(alpha, attn::crow(r, hi), 64);
 #pragma unroll
         for (int d = 0; d < DB; ++d) o_acc[d][r] *= ar;
       }
@@ -555,7 +543,7 @@ __global__ __launch_bounds__(512, 2) void flash_fwd_v2_kernel(
   char* ot = smem + wave * (32 * D * 2);
 #pragma unroll
   for (int r = 0; r < 16; r += 2) {
-    const int row0 = (r & 3) + 8 * (r >> 2) + 4 * hi;  // r even: row(r+1) = row0 + 1
+    const int row0 = attn::crow(r, hi);  // r even: row(r+1) = row0 + 1
     const float il0 = __shfl(inv_l, row0, 64);
     const float il1 = __shfl(inv_l, row0 + 1, 64);
 #pragma unroll
@@ -597,7 +585,7 @@ void launch_fwd(const at::Tensor& qkv, const at::Tensor& slopes, at::Tensor& o,
   auto k = flash_fwd_kernel<D, 512, 2>;
   if constexpr (D == 128) {
     if (!v1)
-      k = (uint32_t)(p_drop * 256.0f + 0.5f) ? flash_fwd_v2_kernel<D, true>
+      k = attn::drop_thr(p_drop) ? flash_fwd_v2_kernel<D, true>
                                              : flash_fwd_v2_kernel<D, false>;
   }
   hipLaunchKernelGGL(k, grid, dim3(512), smem, stream,
@@ -622,12 +610,10 @@ std::vector<at::Tensor> attn_fwd(at::Tensor qkv, at::Tensor slopes, int64_t H_,
   auto sl = slopes.to(at::kFloat).contiguous();
   const float scale = 1.0f / sqrtf((float)D);
   auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
-  switch (D) {
-    case 32: launch_fwd<32>(qkv, sl, o, lse, B, H, T, C, scale, (float)p_drop, (uint32_t)seed, stream); break;
-    case 64: launch_fwd<64>(qkv, sl, o, lse, B, H, T, C, scale, (float)p_drop, (uint32_t)seed, stream); break;
-    case 96: launch_fwd<96>(qkv, sl, o, lse, B, H, T, C, scale, (float)p_drop, (uint32_t)seed, stream); break;
-    case 128: launch_fwd<128>(qkv, sl, o, lse, B, H, T, C, scale, (float)p_drop, (uint32_t)seed, stream); break;
-    default: TORCH_CHECK(false, "attn_fwd: head_dim must be one of 32/64/96/128, got ", D);
-  }
+  const bool ok = attn::with_head_dim(D, [&](auto d) {
+    launch_fwd<decltype(d)::value>(qkv, sl, o, lse, B, H, T, C, scale, (float)p_drop,
+                                   (uint32_t)seed, stream);
+  });
+  TORCH_CHECK(ok, "attn_fwd: head_dim must be one of 32/64/96/128, got ", D);
   return {o, lse};
 }

@@ -6,6 +6,8 @@
 
 #include "common.h"
 
+#include <type_traits>
+
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(2))) int i32x2;
 
@@ -36,7 +38,33 @@ constexpr int TB = 64;       // staged tile rows per iteration
 
 ZTA_DEV int swz(int row, int byte_off) { return byte_off ^ ((row & 7) << 4); }
 
-// B-fragment of mfma_f32_32x32x16_bf16 via hardware transpose read: lane l
+// Row of a 32x32 MFMA C/D tile held by accumulator register r of a lane in
+// half hi = lane >> 5 (the column is lane & 31).
+ZTA_DEV constexpr int crow(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
+
+// Element offsets of the planes of one (b, h) = (bh / H, bh % H) in the
+// packed tensors: q, k and v columns of qkv / dqkv (B, T, 3C), row stride
+// QS = 3C, and the same head's columns of a (B, T, C) tensor (o, dout), row
+// stride C. Head dim D = C / H.
+struct Planes {
+  int h, QS;
+  long base, kbase, vbase, obase;
+};
+template <int D>
+ZTA_DEV Planes planes(int bh, int H, int T, int C) {
+  const int h = bh % H;
+  const int QS = 3 * C;
+  const long base = (long)(bh / H) * T * QS + h * D;
+  return {h, QS, base, base + C, base + 2 * C, (long)(bh / H) * T * C + h * D};
+}
+
+// Dropout of the counter RNG (common.h drop_bits32): a key is kept iff its
+// hash byte >= thr = round(256 p); kept values scale by 256 / (256 - thr).
+// Forward and backward must agree on both, so they are defined once.
+__host__ ZTA_DEV uint32_t drop_thr(float p_drop) { return (uint32_t)(p_drop * 256.0f + 0.5f); }
+ZTA_DEV float drop_inv_keep(uint32_t thr) { return thr ? 256.0f / (256.0f - (float)thr) : 1.0f; }
+
+// B-fragments of mfma_f32_32x32x16_bf16 via hardware transpose reads: lane l
 // receives tile[k0 + 8*(l>>5) + e][j0 + (l&31)] for e = 0..7 from a
 // row-major bf16 LDS tile with 256 B row stride and the T2 XOR swizzle.
 //
@@ -45,11 +73,16 @@ ZTA_DEV int swz(int row, int byte_off) { return byte_off ^ ((row & 7) << 4); }
 // lane l supplies row ((l>>2)&3), column-block 4*(l&3) of a [4][16] tile and
 // receives the column (l%16) of that tile, rows ascending over the 4 regs.
 // Ordering contract for the transpose-read asms below:
-//  * reads + waitcnt MUST be one asm statement: SIInsertWaitcnts cannot see
+//  * a read and its wait must be tied together: SIInsertWaitcnts cannot see
 //    a ds_read inside inline asm, so it inserts no lgkmcnt wait before uses
-//    of its outputs, and a separate waitcnt asm has no dataflow edge to the
+//    of its outputs, and a bare waitcnt asm has no dataflow edge to the
 //    outputs — the scheduler may move the consuming MFMA between read and
-//    wait (observed: register-junk O values with exact lse).
+//    wait (observed: register-junk O values with exact lse). Either both sit
+//    in ONE asm statement, or — the pipelined issue/wait pairs below — the
+//    wait statement takes the fragment registers as "+v" pass-through
+//    operands, so that every consumer depends on it.
+//  * "=&v" (early clobber) keeps a read's destination from aliasing an
+//    address operand that a later read of the same statement still needs.
 //  * the asms carry NO "memory" clobber — a clobber on every fragment read
 //    made each one a full scheduling barrier and serialized the whole MFMA
 //    accumulation loop. Instead the kernel calls lds_acquire() ONCE after
@@ -59,73 +92,17 @@ ZTA_DEV int swz(int row, int byte_off) { return byte_off ^ ((row & 7) << 4); }
 //    (b) pins every later volatile tr-read below the barrier.
 ZTA_DEV void lds_acquire() { asm volatile("" ::: "memory"); }
 
-// "=&v" keeps destinations from aliasing still-live address operands.
-ZTA_DEV bf16x8 tr_frag(const uint16_t* lds, int k0, int j0) {
-  const int l = threadIdx.x & 63;
-  const int colb = (j0 + (l & 16) + 4 * (l & 3)) * 2;
-  const int r0 = k0 + 8 * (l >> 5) + ((l >> 2) & 3);
-  const int a0 = (int)(size_t)((const char*)lds + r0 * 256 + (colb ^ ((r0 & 7) << 4)));
-  const int r1 = r0 + 4;
-  const int a1 = (int)(size_t)((const char*)lds + r1 * 256 + (colb ^ ((r1 & 7) << 4)));
-  union {
-    i32x2 d[2];
-    bf16x8 v;
-  } u;
-  asm volatile(
-      "ds_read_b64_tr_b16 %0, %2\n\t"
-      "ds_read_b64_tr_b16 %1, %3\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&v"(u.d[0]), "=&v"(u.d[1])
-      : "v"(a0), "v"(a1));
-  return u.v;
-}
-
-// Two B-fragments (k0..k0+15 and k0+16..k0+31) in one asm statement: four
-// transpose reads and a single lgkmcnt drain, halving the per-fragment wait
-// + scheduling-barrier cost of tr_frag in the MFMA accumulation loops.
+// Two B-fragments (k0..k0+15 and k0+16..k0+31): four transpose reads.
 struct TrPair {
   bf16x8 a, b;
 };
-
-// Pairs from TWO tiles (same k0/j0) in one asm: eight transpose reads, one
-// drain — for the dKdV loop, which needs dO^T and Q^T fragments per d.
+// Pairs from TWO tiles (same k0/j0): eight transpose reads in one asm — for
+// the dKdV loop, which needs dO^T and Q^T fragments per d.
 struct TrQuad {
   TrPair x, y;
 };
-ZTA_DEV TrQuad tr_frag_quad(const uint16_t* lds_x, const uint16_t* lds_y, int k0,
-                            int j0) {
-  const int l = threadIdx.x & 63;
-  const int colb = (j0 + (l & 16) + 4 * (l & 3)) * 2;
-  const int rb = 8 * (l >> 5) + ((l >> 2) & 3);
-  int ax[4], ay[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int row = k0 + 16 * (i >> 1) + 4 * (i & 1) + rb;
-    const int off = row * 256 + (colb ^ ((row & 7) << 4));
-    ax[i] = (int)(size_t)((const char*)lds_x + off);
-    ay[i] = (int)(size_t)((const char*)lds_y + off);
-  }
-  union {
-    i32x2 d[8];
-    TrQuad f;
-  } u;
-  asm volatile(
-      "ds_read_b64_tr_b16 %0, %8\n\t"
-      "ds_read_b64_tr_b16 %1, %9\n\t"
-      "ds_read_b64_tr_b16 %2, %10\n\t"
-      "ds_read_b64_tr_b16 %3, %11\n\t"
-      "ds_read_b64_tr_b16 %4, %12\n\t"
-      "ds_read_b64_tr_b16 %5, %13\n\t"
-      "ds_read_b64_tr_b16 %6, %14\n\t"
-      "ds_read_b64_tr_b16 %7, %15\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&v"(u.d[0]), "=&v"(u.d[1]), "=&v"(u.d[2]), "=&v"(u.d[3]),
-        "=&v"(u.d[4]), "=&v"(u.d[5]), "=&v"(u.d[6]), "=&v"(u.d[7])
-      : "v"(ax[0]), "v"(ax[1]), "v"(ax[2]), "v"(ax[3]), "v"(ay[0]), "v"(ay[1]),
-        "v"(ay[2]), "v"(ay[3]));
-  return u.f;
-}
-// Software-pipelined form of tr_frag_quad: tr_quad_issue launches the eight
+
+// Software-pipelined transpose reads: tr_quad_issue launches the eight
 // reads with NO wait; tr_quad_wait waits `lgkmcnt(N)` with the fragment
 // registers as pass-through operands so every consumer orders after it.
 // Safety: DS ops complete IN ORDER, so waiting with N = (number of DS ops
@@ -349,31 +326,6 @@ ZTA_DEV void tr_pair_wait(TrPair* q) {
                : "i"(ZTA_SAFE_WAITS ? 0 : N));
 }
 
-ZTA_DEV TrPair tr_frag_pair(const uint16_t* lds, int k0, int j0) {
-  const int l = threadIdx.x & 63;
-  const int colb = (j0 + (l & 16) + 4 * (l & 3)) * 2;
-  const int rb = 8 * (l >> 5) + ((l >> 2) & 3);
-  int a[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int row = k0 + 16 * (i >> 1) + 4 * (i & 1) + rb;
-    a[i] = (int)(size_t)((const char*)lds + row * 256 + (colb ^ ((row & 7) << 4)));
-  }
-  union {
-    i32x2 d[4];
-    TrPair f;
-  } u;
-  asm volatile(
-      "ds_read_b64_tr_b16 %0, %4\n\t"
-      "ds_read_b64_tr_b16 %1, %5\n\t"
-      "ds_read_b64_tr_b16 %2, %6\n\t"
-      "ds_read_b64_tr_b16 %3, %7\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&v"(u.d[0]), "=&v"(u.d[1]), "=&v"(u.d[2]), "=&v"(u.d[3])
-      : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]));
-  return u.f;
-}
-
 // In-register C-layout -> A-fragment transform (T12): 16 f32 values x[r]
 // laid out C[i = crow(r,hi)][j = lane&31] become two bf16x8 A-fragments
 // pa[s2] with lane l holding A[i = l&31][k = s2*16 + 8*(l>>5) + e].
@@ -443,37 +395,17 @@ ZTA_DEV void glds_stats32(const float* a, const float* b, long rowbase, int q0, 
       (__attribute__((address_space(3))) void*)dst, 4, 0, 0);
 }
 
-// T14 tile staging of a 64-row x D-col bf16 tile into a 256 B-stride
-// swizzled LDS image: issue global loads into registers early (hide HBM
-// latency under the previous tile's compute), write to LDS after the
-// barrier. Thread t owns elements {t*8 + c*4096 | c}, row = idx/D.
-template <int D, int NT = 512>
-struct Stage {
-  static constexpr int NC = (TB * D + NT * 8 - 1) / (NT * 8);
-  s16x8 r[NC];
-  // `base` points at row 0 of this (b, h) plane; `rs` is the row stride in
-  // elements (3*C for tensors packed as (B, T, 3C) qkv, C for (B, T, C)).
-  ZTA_DEV void load(const uint16_t* g, long base, int rs, int row0, int T) {
-    const int t = threadIdx.x;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int idx = t * 8 + c * NT * 8;
-      const int rg = row0 + idx / D;
-      r[c] = (idx < TB * D && rg < T)
-                 ? *reinterpret_cast<const s16x8*>(&g[base + (long)rg * rs + idx % D])
-                 : s16x8{};
-    }
+// Host: f(std::integral_constant<int, D>{}) for a head dim the flash kernels
+// are instantiated for; false (f not called) for any other.
+template <class F>
+bool with_head_dim(int D, F&& f) {
+  switch (D) {
+    case 32: f(std::integral_constant<int, 32>{}); return true;
+    case 64: f(std::integral_constant<int, 64>{}); return true;
+    case 96: f(std::integral_constant<int, 96>{}); return true;
+    case 128: f(std::integral_constant<int, 128>{}); return true;
   }
-  ZTA_DEV void store(uint16_t* lds) {
-    const int t = threadIdx.x;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int idx = t * 8 + c * NT * 8;
-      if (idx >= TB * D) break;
-      const int row = idx / D, d = idx % D;
-      *reinterpret_cast<s16x8*>((char*)lds + swz(row, row * 256 + d * 2)) = r[c];
-    }
-  }
-};
+  return false;
+}
 
 }  // namespace attn
