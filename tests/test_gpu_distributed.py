@@ -10,8 +10,8 @@ one GPU, and is here:
     world_size=1, launched from a side HIP stream exactly like the ZeRO
     engine's comm stream (test_rccl_world1_collectives);
   * the full ZeRO-1 world_size=2 step on CUDA tensors over gloo — every
-    bucket view, backward hook, comm-stream wait, wgrad-stream handoff and
-    the sharded AdamW run on the GPU; only the wire transport is gloo
+    bucket view, backward hook, comm-stream wait and the sharded AdamW
+    run on the GPU; only the wire transport is gloo
     (test_zero1_world2_gpu_matches_single) — numerically against a
     single-process GPU run of the combined batch.
 """

@@ -70,7 +70,7 @@ class CausalSelfAttention(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """Returns the PRE-dropout attention output; the residual dropout is
         fused into the Block's residual add (ops.residual_dropout_add)."""
-        qkv = ops.linear(x, self.qkv_w)  # (B, T, 3C); wgrad on the side stream
+        qkv = ops.linear(x, self.qkv_w)  # (B, T, 3C); explicit-GEMM backward
         o = ops.attention_qkv(
             qkv, self.num_head, self.slopes,
             dropout_p=self.dropout_p, training=self.training,

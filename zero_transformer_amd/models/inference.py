@@ -131,10 +131,8 @@ class InferenceAttention(nn.Module):
                 # decode kernel — fully graph-replayable
                 kc.index_copy_(2, static_cache.pos_t, k.to(kc.dtype))
                 vc.index_copy_(2, static_cache.pos_t, v.to(vc.dtype))
-                from ..ops import attention_decode
-
-                out = attention_decode(q.contiguous(), kc, vc, self.slopes,
-                                       s_used=static_cache.len_t)
+                out = ops.attention_decode(q.contiguous(), kc, vc, self.slopes,
+                                           s_used=static_cache.len_t)
                 out = out.transpose(1, 2).reshape(B, T, C)
                 return _proj(out, self.fc_resid.weight), None
             # prefill: fill rows [0, T) and fall through to the SDPA path
@@ -155,10 +153,8 @@ class InferenceAttention(nn.Module):
         ):
             # MI355X-native decode kernel (ops/csrc/attn_decode.hip) — the
             # torch-SDPA path below stays for prefill / CPU
-            from ..ops import attention_decode
-
-            out = attention_decode(q.contiguous(), k.contiguous(), v.contiguous(),
-                                   self.slopes)
+            out = ops.attention_decode(q.contiguous(), k.contiguous(),
+                                       v.contiguous(), self.slopes)
         elif self.slopes is not None:
             mask = _alibi_bias(self.slopes, T, Tk, x.device, q.dtype).unsqueeze(0)
             out = F.scaled_dot_product_attention(q, k, v, attn_mask=mask)

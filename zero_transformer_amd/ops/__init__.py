@@ -41,7 +41,7 @@ def _try_load_extension():
     if _EXT is not None:
         return _EXT
     try:
-        from . import _zta_hip  # in-tree built .so (ops/setup.py build_ext --inplace)
+        from . import _zta_hip  # in-tree built .so (python -m zero_transformer_amd.ops.build)
 
         _EXT = _zta_hip
     except ImportError as e:  # pragma: no cover - exercised only on GPU boxes
@@ -68,46 +68,8 @@ def hip_available() -> bool:
 
 
 # ---------------------------------------------------------------------------
-# Linear with the weight gradient on a side stream
+# Linear with an explicit-GEMM backward
 # ---------------------------------------------------------------------------
-
-_WGRAD_STREAM: Optional["torch.cuda.Stream"] = None
-
-
-def wgrad_stream():
-    """Side stream for weight-gradient GEMMs (lazy, one per process).
-
-    DEFAULT-OFF machinery (see use_wgrad_stream): when ZTA_WGRAD_STREAM=1,
-    weight grads — off the critical path of backward — run here, and the
-    ZeRO adopt-hook copies them into the grad buckets ON this stream
-    (one-directional side-after-main ordering; the main stream orders after
-    it once per step, the comm stream per bucket launch —
-    parallel/zero.py _on_grad_ready / step).
-    """
-    global _WGRAD_STREAM
-    if _WGRAD_STREAM is None:
-        _WGRAD_STREAM = torch.cuda.Stream()
-    return _WGRAD_STREAM
-
-
-def use_wgrad_stream() -> bool:
-    """Whether weight-grad GEMMs (and bucket adopts) use the side stream.
-
-    Default OFF (ZTA_WGRAD_STREAM=1 re-enables): the 2026-09-14 ablation
-    matrix measured the side stream equal-or-worse everywhere — 94.6 vs
-    95.2k tokens/s (accum 1), 103.2 vs 103.8k (accum 4) — and catastrophic
-    at the 0.5M-token config (30.1k vs 112.2k: the side stream lags whole
-    micro-batches behind, record_stream pins each micro's activations until
-    it catches up, and the allocator stalls in retry). Round 1's original
-    motivation (filling attention-backward idle pipes) no longer pays now
-    that dq/dkdv themselves run concurrently on two streams.
-    """
-    import os
-
-    return os.environ.get("ZTA_WGRAD_STREAM", "0") == "1"
-
-
-_use_wgrad_stream = use_wgrad_stream  # internal alias
 
 
 class _LinearFn(torch.autograd.Function):
@@ -120,28 +82,17 @@ class _LinearFn(torch.autograd.Function):
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
         dy = dy.contiguous()
-        dx = dy @ w  # critical path, current stream
-        if not _use_wgrad_stream():
-            dw = dy.reshape(-1, dy.shape[-1]).T @ x.reshape(-1, x.shape[-1])
-            return dx, dw
-        s = wgrad_stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            dw = dy.reshape(-1, dy.shape[-1]).T @ x.reshape(-1, x.shape[-1])
-        # keep x/dy alive for the side stream's GEMM
-        x.record_stream(s)
-        dy.record_stream(s)
-        # dw is handed to AccumulateGrad as a pointer assignment (p.grad is
-        # None between steps); the device-side consumer is the ZeRO hook's
-        # bucket copy, which waits on wgrad_stream first.
+        dx = dy @ w
+        dw = dy.reshape(-1, dy.shape[-1]).T @ x.reshape(-1, x.shape[-1])
         return dx, dw
 
 
 def linear(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
-    """F.linear whose weight gradient runs on the wgrad side stream (GPU).
+    """F.linear whose GPU backward issues its two GEMMs explicitly, on the
+    current stream: dx = dy @ w, then dw = dy^T @ x over the flattened rows.
 
-    Do NOT use for weight-tied layers (multiple grad contributions would
-    accumulate on the main stream unordered against the side stream).
+    Spelled out instead of left to F.linear's autograd so the GEMM calls and
+    layouts stay the ones profiles/tunableop_gfx950.csv is keyed on.
     """
     if x.is_cuda and torch.is_grad_enabled() and w.requires_grad:
         return _LinearFn.apply(x, w)
@@ -207,8 +158,8 @@ def gelu(x: torch.Tensor) -> torch.Tensor:
 def mlp_gelu(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor) -> torch.Tensor:
     """The 4x GELU MLP (reference layers.py:58-77): gelu(x@w1^T)@w2^T.
 
-    GPU training: separate-kernel path (GEMM + gelu kernel + GEMM, weight
-    grads on the side stream). A DGELU-epilogue fused fc2 dgrad was built
+    GPU training: separate-kernel path (GEMM + gelu kernel + GEMM, each
+    GEMM through linear()'s explicit backward). A DGELU-epilogue fused fc2 dgrad was built
     and MEASURED OUT (gpurun 2026-09-14): this gfx950 hipblaslt exposes
     only 2 DGELU-capable algos at the training shape, they regressed the
     step 342 -> 434 ms, and their aux-buffer indexing disagreed with the

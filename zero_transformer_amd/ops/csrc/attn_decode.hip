@@ -3,13 +3,32 @@
 //
 // The training kernels tile MFMA over the T^2 score matrix; decode is a
 // bandwidth-bound row problem (read the cache once), so this is a
-// wave-per-key reduction kernel: one block per (b, h); each wave walks keys
-// j = wave, wave+NW, ... computing score_j = q . k_j (lane-split over D,
-// wave-reduced), keeps wave-local online-softmax state (m, l, fp32 out
-// accumulator in registers), and the four waves merge through LDS at the
-// end. fp32 softmax throughout (the reference's inference mirror used
-// F.scaled_dot_product_attention, torch_compatability/GPT2.py:237 — this is
-// its MI355X-native replacement).
+// wave-per-key reduction split over the key range (split-S), in two kernels:
+//
+//   attn_decode_split_kernel  grid (B*H, SPLITS). Block (bh, split) owns keys
+//     [split*chunk, (split+1)*chunk), chunk = ceil(S/SPLITS). Each of its NW
+//     waves walks keys j = lo+wave, lo+wave+NW, ... computing
+//     score_j = q . k_j (lane-split over D, wave-reduced) and keeps
+//     wave-local online-softmax state (m, l, fp32 out accumulator in
+//     registers); the waves merge through LDS and the block writes one
+//     partial {m, l, acc[D]} to a workspace.
+//   attn_decode_merge_kernel  grid B*H, one wave: merges the SPLITS partials
+//     of its (b, h), normalises and writes out.
+//
+// Why two kernels: with one block per (b, h), decode batch 1 is
+// LATENCY-bound — the grid is B*H = 16 blocks and each wave walks S/NW keys
+// through a serial online-softmax chain (measured 68 us/call at S~160, the
+// dominant decode cost). SPLITS = 8 gives 8x the parallelism and ~1/8 the
+// serial chain. That one-kernel form (and its ZTA_DECODE_NOSPLIT=1 switch)
+// is removed; it can be read at commit c9bc1d5.
+//
+// DPL is D per lane (ceil(D/64)); D up to 256. S_alloc is the allocated
+// cache rows per (b, h) (the base stride); s_used is a device pointer to the
+// LIVE number of cached keys — both kernels' launch arguments stay fixed and
+// the split kernel reads the length in-kernel, so the pair is
+// hipGraph-replayable with a growing cache. fp32 softmax throughout (the
+// reference's inference mirror used F.scaled_dot_product_attention,
+// torch_compatability/GPT2.py:237 — this is its MI355X-native replacement).
 
 #include "common.h"
 
@@ -22,122 +41,6 @@ namespace {
 
 constexpr int NW = 4;  // waves per block
 constexpr float NEG_INF = -3.0e38f;
-
-template <typename T16>
-ZTA_DEV float ld(const T16* p);
-template <>
-ZTA_DEV float ld<uint16_t>(const uint16_t* p) { return bf16_to_f32(*p); }
-
-// DPL: D per lane (D/64); supports D up to 256.
-// S_alloc: allocated cache rows per (b,h) (the base stride); s_used: device
-// pointer to the LIVE number of cached keys — read in-kernel so the launch
-// is hipGraph-replayable with a growing cache.
-template <int DPL>
-__global__ __launch_bounds__(NW * 64) void attn_decode_kernel(
-    const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
-    const uint16_t* __restrict__ v, const float* __restrict__ slopes,
-    uint16_t* __restrict__ out, int H, int S_alloc, const int* __restrict__ s_used,
-    int D, float scale, bool fp16) {
-  const int S = s_used ? *s_used : S_alloc;
-  __shared__ float red[NW * (3 + 64 * DPL)];  // per-wave {m, l, acc[D]}
-  const int bh = blockIdx.x;
-  const int h = bh % H;
-  const long base = (long)bh * S_alloc * D;
-  const int wave = threadIdx.x >> 6;
-  const int lane = threadIdx.x & 63;
-  const float slope = slopes[h];
-
-  // q for this (b, h): each lane holds q[lane + e*64], e < DPL (fp32)
-  float qv[DPL];
-#pragma unroll
-  for (int e = 0; e < DPL; ++e) {
-    const int d = lane + e * 64;
-    qv[e] = d < D ? bf16_to_f32(q[(long)bh * D + d]) : 0.f;
-  }
-
-  float m = NEG_INF, l = 0.f;
-  float acc[DPL];
-#pragma unroll
-  for (int e = 0; e < DPL; ++e) acc[e] = 0.f;
-
-  for (int j = wave; j < S; j += NW) {
-    const uint16_t* kr = &k[base + (long)j * D];
-    float s = 0.f;
-#pragma unroll
-    for (int e = 0; e < DPL; ++e) {
-      const int d = lane + e * 64;
-      if (d < D) s += qv[e] * bf16_to_f32(kr[d]);
-    }
-    s = wave_reduce_sum(s);
-    s = s * scale + slope * (float)(j - (S - 1));  // ALiBi; all keys causal-valid
-    float alpha = 1.f;
-    if (s > m) {
-      alpha = m > 0.5f * NEG_INF ? __expf(m - s) : 0.f;
-      m = s;
-    }
-    const float p = __expf(s - m);
-    l = l * alpha + p;
-    const uint16_t* vr = &v[base + (long)j * D];
-#pragma unroll
-    for (int e = 0; e < DPL; ++e) {
-      const int d = lane + e * 64;
-      acc[e] = acc[e] * alpha + (d < D ? p * bf16_to_f32(vr[d]) : 0.f);
-    }
-  }
-
-  // merge the NW waves' online states
-  float* wr = &red[wave * (3 + 64 * DPL)];
-  if (lane == 0) {
-    wr[0] = m;
-    wr[1] = l;
-  }
-#pragma unroll
-  for (int e = 0; e < DPL; ++e) wr[3 + lane + e * 64] = acc[e];
-  __syncthreads();
-  if (wave == 0) {
-    float mg = NEG_INF;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) mg = fmaxf(mg, red[w * (3 + 64 * DPL)]);
-    float lg = 0.f;
-    float og[DPL];
-#pragma unroll
-    for (int e = 0; e < DPL; ++e) og[e] = 0.f;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-      const float mw = red[w * (3 + 64 * DPL)];
-      const float f = mw > 0.5f * NEG_INF ? __expf(mw - mg) : 0.f;
-      lg += red[w * (3 + 64 * DPL) + 1] * f;
-#pragma unroll
-      for (int e = 0; e < DPL; ++e)
-        og[e] += red[w * (3 + 64 * DPL) + 3 + lane + e * 64] * f;
-    }
-    const float inv = lg > 0.f ? 1.f / lg : 0.f;
-#pragma unroll
-    for (int e = 0; e < DPL; ++e) {
-      const int d = lane + e * 64;
-      if (d < D) {
-        const float o = og[e] * inv;
-        if (fp16) {
-          __half hv = __float2half(o);
-          out[(long)bh * D + d] = *reinterpret_cast<uint16_t*>(&hv);
-        } else {
-          out[(long)bh * D + d] = f32_to_bf16(o);
-        }
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Split-S variant: the single-block kernel above is LATENCY-bound at decode
-// batch 1 (grid = B*H = 16 blocks; each wave walks S/NW keys through a
-// serial online-softmax chain — measured 68 us/call at S~160, the dominant
-// decode cost). Here the key range is split over SPLITS blocks per (b, h)
-// (grid B*H x SPLITS), each writing a partial {m, l, acc} to a workspace;
-// a second tiny kernel merges the partials. 8x the parallelism, ~1/8 the
-// serial chain. Both kernels read the live length from s_used so the pair
-// stays hipGraph-replayable.
-// ---------------------------------------------------------------------------
 
 template <int DPL, bool F16>
 __global__ __launch_bounds__(NW * 64) void attn_decode_split_kernel(
@@ -275,96 +178,6 @@ __global__ __launch_bounds__(64) void attn_decode_merge_kernel(
   }
 }
 
-// fp16 cache variant reads via __half
-template <int DPL>
-__global__ __launch_bounds__(NW * 64) void attn_decode_kernel_f16(
-    const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
-    const uint16_t* __restrict__ v, const float* __restrict__ slopes,
-    uint16_t* __restrict__ out, int H, int S_alloc, const int* __restrict__ s_used,
-    int D, float scale) {
-  const int S = s_used ? *s_used : S_alloc;
-  __shared__ float red[NW * (3 + 64 * DPL)];
-  const int bh = blockIdx.x;
-  const int h = bh % H;
-  const long base = (long)bh * S_alloc * D;
-  const int wave = threadIdx.x >> 6;
-  const int lane = threadIdx.x & 63;
-  const float slope = slopes[h];
-  auto h2f = [](uint16_t u) {
-    __half hv = *reinterpret_cast<__half*>(&u);
-    return __half2float(hv);
-  };
-  float qv[DPL];
-#pragma unroll
-  for (int e = 0; e < DPL; ++e) {
-    const int d = lane + e * 64;
-    qv[e] = d < D ? h2f(q[(long)bh * D + d]) : 0.f;
-  }
-  float m = NEG_INF, l = 0.f;
-  float acc[DPL];
-#pragma unroll
-  for (int e = 0; e < DPL; ++e) acc[e] = 0.f;
-  for (int j = wave; j < S; j += NW) {
-    const uint16_t* kr = &k[base + (long)j * D];
-    float s = 0.f;
-#pragma unroll
-    for (int e = 0; e < DPL; ++e) {
-      const int d = lane + e * 64;
-      if (d < D) s += qv[e] * h2f(kr[d]);
-    }
-    s = wave_reduce_sum(s);
-    s = s * scale + slope * (float)(j - (S - 1));
-    float alpha = 1.f;
-    if (s > m) {
-      alpha = m > 0.5f * NEG_INF ? __expf(m - s) : 0.f;
-      m = s;
-    }
-    const float p = __expf(s - m);
-    l = l * alpha + p;
-    const uint16_t* vr = &v[base + (long)j * D];
-#pragma unroll
-    for (int e = 0; e < DPL; ++e) {
-      const int d = lane + e * 64;
-      acc[e] = acc[e] * alpha + (d < D ? p * h2f(vr[d]) : 0.f);
-    }
-  }
-  float* wr = &red[wave * (3 + 64 * DPL)];
-  if (lane == 0) {
-    wr[0] = m;
-    wr[1] = l;
-  }
-#pragma unroll
-  for (int e = 0; e < DPL; ++e) wr[3 + lane + e * 64] = acc[e];
-  __syncthreads();
-  if (wave == 0) {
-    float mg = NEG_INF;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) mg = fmaxf(mg, red[w * (3 + 64 * DPL)]);
-    float lg = 0.f;
-    float og[DPL];
-#pragma unroll
-    for (int e = 0; e < DPL; ++e) og[e] = 0.f;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-      const float mw = red[w * (3 + 64 * DPL)];
-      const float f = mw > 0.5f * NEG_INF ? __expf(mw - mg) : 0.f;
-      lg += red[w * (3 + 64 * DPL) + 1] * f;
-#pragma unroll
-      for (int e = 0; e < DPL; ++e)
-        og[e] += red[w * (3 + 64 * DPL) + 3 + lane + e * 64] * f;
-    }
-    const float inv = lg > 0.f ? 1.f / lg : 0.f;
-#pragma unroll
-    for (int e = 0; e < DPL; ++e) {
-      const int d = lane + e * 64;
-      if (d < D) {
-        __half hv = __float2half(og[e] * inv);
-        out[(long)bh * D + d] = *reinterpret_cast<uint16_t*>(&hv);
-      }
-    }
-  }
-}
-
 }  // namespace
 
 // `s_used`: optional 1-element int32 CUDA tensor with the live cache length
@@ -390,20 +203,10 @@ at::Tensor attn_decode(at::Tensor q, at::Tensor k, at::Tensor v,
   const bool f16 = q.scalar_type() == at::kHalf;
   TORCH_CHECK(f16 || q.scalar_type() == at::kBFloat16, "bf16 or fp16 only");
 
-  // The split-S two-kernel path is the default: at decode batch 1 the
-  // one-kernel form had B*H = 16 blocks and a serial per-key chain
-  // (measured 68 us/call); splitting the key range over 8 blocks per
-  // (b, h) cuts the chain 8x and fills the CUs. The one-kernel form stays
-  // selectable for A/B via ZTA_DECODE_NOSPLIT=1.
-  static const bool nosplit = [] {
-    const char* e = getenv("ZTA_DECODE_NOSPLIT");
-    return e && e[0] == '1';
-  }();
-  if (!nosplit) {
-    const int splits = 8;
-    auto part = at::empty({(long)B * H, splits, 2 + 64 * (long)dpl},
-                          q.options().dtype(at::kFloat));
-    dim3 grid(B * H, splits);
+  const int splits = 8;  // blocks per (b, h) — see the file header
+  auto part = at::empty({(long)B * H, splits, 2 + 64 * (long)dpl},
+                        q.options().dtype(at::kFloat));
+  dim3 grid(B * H, splits);
 #define LAUNCH_SPLIT(DPL, F16V)                                                \
   do {                                                                         \
     hipLaunchKernelGGL((attn_decode_split_kernel<DPL, F16V>), grid,            \
@@ -417,36 +220,13 @@ at::Tensor attn_decode(at::Tensor q, at::Tensor k, at::Tensor v,
                        dim3(64), 0, stream, part.data_ptr<float>(),            \
                        (uint16_t*)out.data_ptr(), D, splits);                  \
   } while (0)
-    switch (dpl) {
-      case 1: if (f16) LAUNCH_SPLIT(1, true); else LAUNCH_SPLIT(1, false); break;
-      case 2: if (f16) LAUNCH_SPLIT(2, true); else LAUNCH_SPLIT(2, false); break;
-      case 3: if (f16) LAUNCH_SPLIT(3, true); else LAUNCH_SPLIT(3, false); break;
-      case 4: if (f16) LAUNCH_SPLIT(4, true); else LAUNCH_SPLIT(4, false); break;
-      default: TORCH_CHECK(false, "bad head_dim");
-    }
-#undef LAUNCH_SPLIT
-    return out;
-  }
-#define LAUNCH(DPL)                                                                \
-  if (f16)                                                                         \
-    hipLaunchKernelGGL(attn_decode_kernel_f16<DPL>, dim3(B * H), dim3(NW * 64), 0, \
-                       stream, (const uint16_t*)q.data_ptr(),                      \
-                       (const uint16_t*)k.data_ptr(), (const uint16_t*)v.data_ptr(),\
-                       sl.data_ptr<float>(), (uint16_t*)out.data_ptr(), H, S_alloc,\
-                       sp, D, scale);                                              \
-  else                                                                             \
-    hipLaunchKernelGGL(attn_decode_kernel<DPL>, dim3(B * H), dim3(NW * 64), 0,     \
-                       stream, (const uint16_t*)q.data_ptr(),                      \
-                       (const uint16_t*)k.data_ptr(), (const uint16_t*)v.data_ptr(),\
-                       sl.data_ptr<float>(), (uint16_t*)out.data_ptr(), H, S_alloc,\
-                       sp, D, scale, false)
   switch (dpl) {
-    case 1: LAUNCH(1); break;
-    case 2: LAUNCH(2); break;
-    case 3: LAUNCH(3); break;
-    case 4: LAUNCH(4); break;
+    case 1: if (f16) LAUNCH_SPLIT(1, true); else LAUNCH_SPLIT(1, false); break;
+    case 2: if (f16) LAUNCH_SPLIT(2, true); else LAUNCH_SPLIT(2, false); break;
+    case 3: if (f16) LAUNCH_SPLIT(3, true); else LAUNCH_SPLIT(3, false); break;
+    case 4: if (f16) LAUNCH_SPLIT(4, true); else LAUNCH_SPLIT(4, false); break;
     default: TORCH_CHECK(false, "bad head_dim");
   }
-#undef LAUNCH
+#undef LAUNCH_SPLIT
   return out;
 }

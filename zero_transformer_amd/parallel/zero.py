@@ -93,8 +93,6 @@ class ZeRO1Optimizer:
         self.param_dtype = param_dtype or uniq[0][1].dtype
         self.overlap_comm = overlap_comm and self.device.type == "cuda" and self.world > 1
         self._sync = accum_steps == 1
-        # adopt grads on the wgrad side stream (see _on_grad_ready)
-        self._wgrad_adopt = self.device.type == "cuda" and ops.use_wgrad_stream()
         self._comm_stream = (
             torch.cuda.Stream(device=self.device) if self.overlap_comm else None
         )
@@ -176,31 +174,18 @@ class ZeRO1Optimizer:
         # and reset p.grad to None so every backward ASSIGNS a fresh tensor
         # instead of read-modify-writing zeroed memory.
         #
-        # Stream discipline: side-stream weight grads (ops.linear) must be
-        # ordered before the bucket write. Waiting the wgrad-stream TAIL
-        # from the main stream per param was measured CATASTROPHIC under
-        # grad accumulation (main<->side ping-pong serialized both streams:
-        # 29.6k vs 111.6k tokens/s on the 0.5M-token config, gpurun
-        # 2026-09-14). Instead the adopt copy itself runs ON the wgrad
-        # stream — a one-directional side-after-main dependency; the main
-        # stream waits the side stream exactly once per step (step()), and
-        # the comm stream waits it per bucket launch.
+        # Stream discipline: the weight-grad GEMMs and this bucket write both
+        # run on the current stream, so they need no ordering; only the comm
+        # stream waits (_launch_reduce). Moving the weight grads and this
+        # write to a side stream was measured 3.7x slower under grad
+        # accumulation and removed — see profiles/PERF.md before rebuilding.
         view = self._grad_view[id(p)]
         g = p.grad
         if g is not view:
             first = id(p) not in self._accumulated
             if first:
                 self._accumulated.add(id(p))
-            if g.is_cuda and self._wgrad_adopt:
-                from .. import ops as _ops
-
-                s = _ops.wgrad_stream()
-                s.wait_stream(torch.cuda.current_stream(self.device))
-                with torch.cuda.stream(s):
-                    view.copy_(g) if first else view.add_(g)
-                g.record_stream(s)
-            else:
-                view.copy_(g) if first else view.add_(g)
+            view.copy_(g) if first else view.add_(g)
             p.grad = None
         if not self._sync:
             return
@@ -212,14 +197,9 @@ class ZeRO1Optimizer:
     def _launch_reduce(self, b: Bucket):
         if self.overlap_comm:
             self._comm_stream.wait_stream(torch.cuda.current_stream(self.device))
-            if self._wgrad_adopt:
-                # bucket contents were written on the wgrad stream
-                self._comm_stream.wait_stream(ops.wgrad_stream())
             with torch.cuda.stream(self._comm_stream):
                 comm.reduce_scatter_mean(b.grad_shard, b.flat_grad)
         else:
-            if self._wgrad_adopt and self.device.type == "cuda":
-                torch.cuda.current_stream(self.device).wait_stream(ops.wgrad_stream())
             comm.reduce_scatter_mean(b.grad_shard, b.flat_grad)
 
     # ------------------------------------------------------------------
@@ -228,10 +208,6 @@ class ZeRO1Optimizer:
         assert self._sync, "step() called while grad sync disabled"
         self.step_count += 1
         lr = float(self.lr(self.step_count))
-        if self._wgrad_adopt:
-            # single main-after-side order point per step: all side-stream
-            # bucket writes (and the wgrad GEMMs feeding them) are visible
-            torch.cuda.current_stream(self.device).wait_stream(ops.wgrad_stream())
         # any bucket whose hook never fired (e.g. unused param) — zero the
         # stale regions (the flat buffer holds last step's values until a
         # hook adopts a fresh grad) and reduce now
