@@ -7,6 +7,10 @@ Two modes:
           POST /generate {"prompt": ..., "max_new_tokens": ..., ...}
           (FastAPI + uvicorn instead of the reference's Gradio UI — same
           streaming KV-cached generation + samplers, reference app.py:42-142.)
+          POST /generate_batch {"prompts": [...], ...same options...}
+            -> {"completions": [...]}: prompts of any lengths, one batch
+  Several --prompt flags on the CLI go through the same batched path and
+  print one completion per line.
 
 Tokenizer: GPT-NeoX-20B via transformers when its assets are cached locally
 (reference app.py:27); otherwise a byte-level fallback so the app works on
@@ -20,6 +24,7 @@ import argparse
 import torch
 
 from torch_compatability.GPT2 import model_getter
+from zero_transformer_amd.models.inference import generate_batch
 from zero_transformer_amd.models.sampling import generate_stream
 
 
@@ -62,11 +67,34 @@ def generate_text(model, tok, device, prompt: str, **kw) -> str:
     return tok.decode(out)
 
 
+def generate_texts(model, tok, prompts, **kw) -> list:
+    """Completions for several prompts of any lengths in one ragged batch
+    (inference.generate_batch: per-sequence KV lengths, batched sampling)."""
+    outs = generate_batch(model, [tok.encode(s) for s in prompts],
+                          kw.pop("max_new_tokens"),
+                          eos_token=getattr(tok, "eos_token_id", None), **kw)
+    return [tok.decode(o) for o in outs]
+
+
+def _options(req: dict) -> dict:
+    """Sampling options of a request body, with the server defaults."""
+    return dict(
+        max_new_tokens=int(req.get("max_new_tokens", 128)),
+        temperature=float(req.get("temperature", 0.8)),
+        top_k=int(req.get("top_k", 0)),
+        top_p=float(req.get("top_p", 0.95)),
+        repetition_penalty=float(req.get("repetition_penalty", 1.1)),
+        sample=not bool(req.get("greedy", False)),
+    )
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--model-size", default="test")
     p.add_argument("--checkpoint", default=None)
-    p.add_argument("--prompt", default=None)
+    p.add_argument("--prompt", action="append", default=None,
+                   help="repeat for several prompts: they run as one batch "
+                   "and print one completion per line")
     p.add_argument("--max-new-tokens", type=int, default=128)
     p.add_argument("--temperature", type=float, default=0.8)
     p.add_argument("--top-k", type=int, default=0)
@@ -101,8 +129,12 @@ def main():
         app = build_app(model, tok, device)
         uvicorn.run(app, host=args.host, port=args.port)
     else:
-        prompt = args.prompt or "Hello"
-        print(prompt + generate_text(model, tok, device, prompt, **kw))
+        prompts = args.prompt or ["Hello"]
+        if len(prompts) == 1:
+            print(prompts[0] + generate_text(model, tok, device, prompts[0], **kw))
+        else:
+            for prompt, text in zip(prompts, generate_texts(model, tok, prompts, **kw)):
+                print((prompt + text).replace("\n", "\\n"))
 
 
 def build_app(model, tok, device):
@@ -114,16 +146,13 @@ def build_app(model, tok, device):
 
     @app.post("/generate")
     def generate(req: dict = Body(...)):
-        text = generate_text(
-            model, tok, device, str(req["prompt"]),
-            max_new_tokens=int(req.get("max_new_tokens", 128)),
-            temperature=float(req.get("temperature", 0.8)),
-            top_k=int(req.get("top_k", 0)),
-            top_p=float(req.get("top_p", 0.95)),
-            repetition_penalty=float(req.get("repetition_penalty", 1.1)),
-            sample=not bool(req.get("greedy", False)),
-        )
+        text = generate_text(model, tok, device, str(req["prompt"]), **_options(req))
         return {"completion": text}
+
+    @app.post("/generate_batch")
+    def generate_batch_(req: dict = Body(...)):
+        prompts = [str(s) for s in req["prompts"]]
+        return {"completions": generate_texts(model, tok, prompts, **_options(req))}
 
     @app.get("/")
     def index():

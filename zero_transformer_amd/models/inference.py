@@ -11,7 +11,7 @@ loss. Loads / saves the .pth state-dict contract
 
 from __future__ import annotations
 
-from typing import List, Optional, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
@@ -31,12 +31,14 @@ def _proj(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
 
 
 class StaticKVCache:
-    """Preallocated per-layer KV buffers with a DEVICE-side length counter.
+    """Preallocated per-layer KV buffers with DEVICE-side per-sequence lengths.
 
     Makes the whole decode step hipGraph-replayable: the cache write position
     and the decode-attention kernel's live length both come from device
-    memory (ops.attention_decode reads `len_t` in-kernel), so one captured
-    graph serves every token as the cache grows.
+    memory (ops.attention_decode_append reads `len_t` in-kernel and appends
+    the new row at len - 1), so one captured graph serves every token as the
+    cache grows. `len_t` is (batch,) int32: sequences of a batch may differ
+    in length.
     """
 
     def __init__(self, n_layers: int, batch: int, heads: int, head_dim: int,
@@ -45,21 +47,20 @@ class StaticKVCache:
                               dtype=dtype) for _ in range(n_layers)]
         self.v = [torch.zeros(batch, heads, max_ctx, head_dim, device=device,
                               dtype=dtype) for _ in range(n_layers)]
-        self.len_t = torch.zeros(1, dtype=torch.int32, device=device)
-        # write position (= len - 1) as int64, maintained here so the per-
-        # layer cache writes need no to(long)/sub kernels (those two tiny
-        # launches per layer were ~0.2 ms/token)
-        self.pos_t = torch.zeros(1, dtype=torch.int64, device=device)
+        self.len_t = torch.zeros(batch, dtype=torch.int32, device=device)
         self.max_ctx = max_ctx
 
-    def advance(self, n: int = 1):
-        # device adds: correct inside a captured graph replay
+    def advance(self, n=1):
+        """Add an int, or a (B,) int32 device tensor (0/1 per sequence: only
+        the active ones grow). Device adds: correct inside a graph replay."""
         self.len_t += n
-        self.pos_t += n
 
-    def set_len(self, n: int):
-        self.len_t.fill_(n)
-        self.pos_t.fill_(n - 1)
+    def set_len(self, n):
+        """An int (every sequence) or a length-B sequence / tensor."""
+        if isinstance(n, int):
+            self.len_t.fill_(n)
+        else:
+            self.len_t.copy_(torch.as_tensor(n, dtype=torch.int32))
 
 
 def _alibi_bias(slopes: torch.Tensor, Tq: int, Tk: int, device, dtype) -> torch.Tensor:
@@ -106,7 +107,7 @@ class InferenceAttention(nn.Module):
     ):
         B, T, C = x.shape
         H, D = self.num_head, self.head_dim
-        if T == 1 and x.is_cuda:
+        if T == 1 and (x.is_cuda or static_cache is not None):
             # decode: one fused (3C, C) GEMV instead of three launches (the
             # fused weight is materialized lazily; same total weight-stream
             # bytes, 1/3 the kernel launches and a fuller grid)
@@ -115,6 +116,15 @@ class InferenceAttention(nn.Module):
                     [self.query.weight, self.key.weight, self.value.weight], dim=0
                 ).contiguous()
             qkv = ops.decode_linear(x, self._qkv_w)
+            if static_cache is not None:
+                # the kernel reads q / k / v straight from the projection
+                # row, appends k / v at device position len-1 (len already
+                # advanced for this token, per sequence) and attends over
+                # the live cache — fully graph-replayable
+                out = ops.attention_decode_append(
+                    qkv, static_cache.k[layer_idx], static_cache.v[layer_idx],
+                    H, self.slopes, static_cache.len_t)
+                return _proj(out, self.fc_resid.weight), None
             q, k, v = qkv.split(C, dim=-1)
             q = q.view(B, T, H, D).transpose(1, 2)
             k = k.view(B, T, H, D).transpose(1, 2)
@@ -125,16 +135,6 @@ class InferenceAttention(nn.Module):
             v = _proj(x, self.value.weight).view(B, T, H, D).transpose(1, 2)
         if static_cache is not None:
             kc, vc = static_cache.k[layer_idx], static_cache.v[layer_idx]
-            if T == 1:
-                # decode: write at device position len-1 (len already advanced
-                # for this token), attend over the live cache via the native
-                # decode kernel — fully graph-replayable
-                kc.index_copy_(2, static_cache.pos_t, k.to(kc.dtype))
-                vc.index_copy_(2, static_cache.pos_t, v.to(vc.dtype))
-                out = ops.attention_decode(q.contiguous(), kc, vc, self.slopes,
-                                           s_used=static_cache.len_t)
-                out = out.transpose(1, 2).reshape(B, T, C)
-                return _proj(out, self.fc_resid.weight), None
             # prefill: fill rows [0, T) and fall through to the SDPA path
             idxs = torch.arange(T, device=x.device)
             kc.index_copy_(2, idxs, k.to(kc.dtype))
@@ -304,6 +304,36 @@ class GPT2(nn.Module):
         return idx
 
 
+# Graph warm-up + capture run the decode step this many times, writing
+# scratch KV rows len..len+2 of every sequence before the lengths are rewound:
+# callers size the static buffers with that headroom (clamped to num_ctx) and
+# skip capture when the longest prompt is within 3 rows of the context limit.
+GRAPH_SCRATCH_ROWS = 3
+
+# generate_batch asks the device whether every row has finished once per this
+# many steps: one host sync per check, at most this many - 1 wasted steps.
+FINISHED_CHECK_EVERY = 16
+
+
+def capture_decode_step(step, cache: StaticKVCache, lens):
+    """Warm `step` up on a side stream, capture it in a hipGraph and rewind
+    the cache lengths to `lens` (an int or one length per sequence): the
+    warm-up and the capture advanced every sequence and wrote 3 fake rows
+    behind it, which real tokens overwrite as the lengths re-advance.
+    Returns (graph, step's captured output buffer)."""
+    warm = torch.cuda.Stream()
+    warm.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(warm):
+        for _ in range(GRAPH_SCRATCH_ROWS - 1):
+            step()
+    torch.cuda.current_stream().wait_stream(warm)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        out = step()
+    cache.set_len(lens)
+    return graph, out
+
+
 @torch.no_grad()
 def generate_fast(
     model: "GPT2",
@@ -321,17 +351,15 @@ def generate_fast(
     H = model.blocks[0].attn.num_head
     D = model.blocks[0].attn.head_dim
     max_ctx = min(model.num_ctx, T0 + max_new_tokens)
-    # Graph warmup + capture below run step() 3 times, writing scratch KV
-    # rows T0..T0+2 before the length counter is rewound — size the static
-    # buffers with that headroom (clamped to num_ctx) and skip capture when
-    # the prompt is within 3 rows of the context limit.
-    cache_rows = min(model.num_ctx, max_ctx + 3)
-    use_graph = use_graph and dev.type == "cuda" and cache_rows - T0 >= 3
+    cache_rows = min(model.num_ctx, max_ctx + GRAPH_SCRATCH_ROWS)
+    use_graph = (use_graph and dev.type == "cuda"
+                 and cache_rows - T0 >= GRAPH_SCRATCH_ROWS)
     cache = StaticKVCache(model.N, B, H, D, cache_rows, dev, p.dtype)
 
-    # prefill
-    logits = model(idx, static_cache=cache)
+    # prefill. The length goes first: a one-token prompt prefills through
+    # the decode step, which appends at row len - 1 (T0 > 1 never reads it)
     cache.set_len(T0)
+    logits = model(idx, static_cache=cache)
     cur = logits[:, -1:].argmax(-1)  # (B, 1) — static input buffer
     out_tokens = [cur.clone()]
 
@@ -341,21 +369,10 @@ def generate_fast(
 
     graph = None
     if use_graph:
-        warm = torch.cuda.Stream()
-        warm.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(warm):
-            for _ in range(2):
-                step()
-        torch.cuda.current_stream().wait_stream(warm)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            logits_buf = step()
-        # warmup + capture advanced/wrote 3 fake tokens at rows T0..T0+2;
-        # rewind: real tokens overwrite those rows as len re-advances
-        cache.set_len(T0)
+        graph, logits_buf = capture_decode_step(step, cache, T0)
 
     for i in range(max_new_tokens - 1):
-        if cache.len_t is not None and T0 + 1 + i >= max_ctx:
+        if T0 + 1 + i >= max_ctx:
             break
         if graph is not None:
             graph.replay()
@@ -365,6 +382,109 @@ def generate_fast(
         cur.copy_(nxt)
         out_tokens.append(nxt.clone())
     return torch.cat([idx] + out_tokens, dim=1)
+
+
+@torch.no_grad()
+def generate_batch(
+    model: "GPT2",
+    prompts: Sequence[Sequence[int]],
+    max_new_tokens: int,
+    *,
+    eos_token: Optional[int] = None,
+    sample: bool = False,
+    temperature: float = 1.0,
+    top_k: int = 0,
+    top_p: float = 1.0,
+    repetition_penalty: float = 1.0,
+    use_graph: bool = True,
+) -> List[List[int]]:
+    """Batched generation for prompts of DIFFERENT lengths (each >= 1 and
+    <= model.num_ctx), on the model's device.
+
+    Returns the generated tokens per prompt, without the prompt, cut before
+    the first `eos_token`. Row b yields at most
+    min(max_new_tokens, num_ctx - len(prompts[b])) tokens — generate_fast's
+    rule per sequence.
+
+    One right-padded prefill fills the static cache: ALiBi's bias depends
+    only on j - i and the pad keys lie in every real token's future, so the
+    real rows are exact; pad K/V land in rows >= len(prompts[b]), which the
+    decode kernel never reads and later tokens overwrite. Decode then runs
+    with per-sequence lengths (StaticKVCache.len_t), sampling batched and on
+    device (no per-token host sync). Finished rows stop advancing, keep
+    being fed their last token and their outputs are discarded.
+    """
+    from .sampling import sample_batch
+
+    B = len(prompts)
+    lens = [len(p) for p in prompts]
+    assert B >= 1 and min(lens) >= 1, "generate_batch: every prompt needs >= 1 token"
+    assert max(lens) <= model.num_ctx, "generate_batch: prompt longer than num_ctx"
+    if max_new_tokens <= 0:
+        return [[] for _ in prompts]
+    p = next(model.parameters())
+    dev = p.device
+    H = model.blocks[0].attn.num_head
+    D = model.blocks[0].attn.head_dim
+    limits = [min(max_new_tokens, model.num_ctx - n) for n in lens]
+    max_ctx = max(n + m for n, m in zip(lens, limits))
+    cache_rows = min(model.num_ctx, max_ctx + GRAPH_SCRATCH_ROWS)
+    use_graph = (use_graph and dev.type == "cuda"
+                 and cache_rows - max(lens) >= GRAPH_SCRATCH_ROWS)
+    cache = StaticKVCache(model.N, B, H, D, cache_rows, dev, p.dtype)
+
+    idx = torch.zeros(B, max(lens), dtype=torch.long)
+    seen = torch.zeros(B, model.vocab_size, dtype=torch.bool)
+    for b, pr in enumerate(prompts):
+        row = torch.as_tensor(list(pr), dtype=torch.long)
+        idx[b, : lens[b]] = row
+        seen[b, row] = True
+    idx, seen = idx.to(dev), seen.to(dev)
+    lens_t = torch.tensor(lens, dtype=torch.int32, device=dev)
+    limit_t = torch.tensor(limits, device=dev)
+
+    # lengths first: prompts of one token prefill through the decode step
+    cache.set_len(lens_t)
+    logits = model(idx, static_cache=cache)
+    last = logits[torch.arange(B, device=dev), lens_t.long() - 1]  # (B, V)
+
+    cur = idx.new_zeros((B, 1))  # static input buffers of the decode step
+    active = torch.ones(B, dtype=torch.int32, device=dev)
+
+    def step():
+        cache.advance(active)
+        return model(cur, static_cache=cache)
+
+    graph = None
+    if use_graph:
+        graph, logits_buf = capture_decode_step(step, cache, lens_t)
+
+    out = torch.full((B, max_new_tokens), -1, dtype=torch.long, device=dev)
+    finished = limit_t <= 0
+    for g in range(max_new_tokens):
+        nxt = sample_batch(last, seen, temperature, top_k, top_p,
+                           repetition_penalty, sample)  # (B,)
+        emit = ~finished
+        if eos_token is not None:
+            emit &= nxt != eos_token
+        out[:, g] = torch.where(emit, nxt, -1)
+        finished = ~emit | (limit_t <= g + 1)
+        if g + 1 == max_new_tokens:
+            break
+        if (g + 1) % FINISHED_CHECK_EVERY == 0 and bool(finished.all()):
+            break
+        seen.scatter_(1, nxt.view(B, 1), True)
+        cur.copy_(torch.where(finished.view(B, 1), cur, nxt.view(B, 1)))
+        active.copy_(~finished)
+        if graph is not None:
+            graph.replay()
+            last = logits_buf[:, -1]
+        else:
+            last = step()[:, -1]
+    res = []
+    for row in out.tolist():
+        res.append(row[: row.index(-1)] if -1 in row else row)
+    return res
 
 
 def model_getter(

@@ -23,6 +23,20 @@ def apply_repetition_penalty(
     return logits
 
 
+def apply_repetition_penalty_batched(
+    logits: torch.Tensor, seen: torch.Tensor, penalty: float
+) -> torch.Tensor:
+    """apply_repetition_penalty for a batch, on device: logits (B, V), seen
+    (B, V) bool marking each row's prompt and generated tokens (kept up to
+    date with scatter_). Row b gets what apply_repetition_penalty gives it
+    alone with the tokens seen[b] marks. Never writes to `logits`: returns a
+    new tensor, or `logits` itself when penalty == 1.0."""
+    if penalty == 1.0:
+        return logits
+    pen = torch.where(logits > 0, logits / penalty, logits * penalty)
+    return torch.where(seen, pen, logits)
+
+
 def top_k_filter(logits: torch.Tensor, k: int) -> torch.Tensor:
     """Keep the k highest logits (reference app.py:111-115)."""
     if k <= 0:
@@ -57,6 +71,24 @@ def _sample_next(logits, generated, temperature, top_k, top_p,
     return int(torch.multinomial(probs, 1).item()) if sample else int(probs.argmax().item())
 
 
+def sample_batch(logits, seen, temperature, top_k, top_p,
+                 repetition_penalty, sample) -> torch.Tensor:
+    """_sample_next for a batch without leaving the device: logits (B, V),
+    seen as in apply_repetition_penalty_batched -> (B,) int64 token ids.
+    Greedy takes the argmax of the penalised logits directly (temperature
+    and the filters keep the maximum where it is)."""
+    lg = apply_repetition_penalty_batched(logits, seen, repetition_penalty)
+    if not sample:
+        return lg.argmax(-1)
+    lg = lg / max(temperature, 1e-5)
+    if top_k:
+        lg = top_k_filter(lg, top_k)
+    if top_p < 1.0:
+        lg = top_p_filter(lg, top_p)
+    probs = F.softmax(lg.float(), dim=-1)
+    return torch.multinomial(probs, 1).squeeze(-1)
+
+
 @torch.no_grad()
 def generate_stream(
     model,
@@ -79,24 +111,27 @@ def generate_stream(
     dynamic layer_past path.
     """
     model.eval()
-    assert idx.shape[0] == 1, "generate_stream streams a single prompt (B=1); use inference.generate_fast for batched greedy decoding"
+    assert idx.shape[0] == 1, "generate_stream streams a single prompt (B=1); use inference.generate_batch for batched decoding"
     generated: List[int] = idx[0].tolist()
     kw = (temperature, top_k, top_p, repetition_penalty, sample)
 
     if idx.is_cuda:
-        from .inference import StaticKVCache
+        from .inference import (GRAPH_SCRATCH_ROWS, StaticKVCache,
+                                capture_decode_step)
 
         B, T0 = idx.shape
         dev = idx.device
         H = model.blocks[0].attn.num_head
         D = model.blocks[0].attn.head_dim
         max_ctx = min(model.num_ctx, T0 + max_new_tokens)
-        rows = min(model.num_ctx, max_ctx + 3)  # graph-warmup headroom
-        use_graph = use_graph and rows - T0 >= 3
+        rows = min(model.num_ctx, max_ctx + GRAPH_SCRATCH_ROWS)
+        use_graph = use_graph and rows - T0 >= GRAPH_SCRATCH_ROWS
         cache = StaticKVCache(model.N, B, H, D, rows, dev,
                               next(model.parameters()).dtype)
-        logits = model(idx, static_cache=cache)
+        # length first: a one-token prompt prefills through the decode
+        # step, which appends at row len - 1 (T0 > 1 never reads it)
         cache.set_len(T0)
+        logits = model(idx, static_cache=cache)
         cur = idx.new_zeros((B, 1))
 
         def step():
@@ -105,16 +140,7 @@ def generate_stream(
 
         graph = None
         if use_graph:
-            warm = torch.cuda.Stream()
-            warm.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(warm):
-                for _ in range(2):
-                    step()
-            torch.cuda.current_stream().wait_stream(warm)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                logits_buf = step()
-            cache.set_len(T0)
+            graph, logits_buf = capture_decode_step(step, cache, T0)
 
         for i in range(max_new_tokens):
             nxt = _sample_next(logits, generated, *kw)

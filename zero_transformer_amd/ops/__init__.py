@@ -331,9 +331,11 @@ def attention_decode(
     (B,H,1,D). ALiBi bias slope*(j - (S-1)); every cached key is
     causal-valid for the one query. Inference only (no autograd).
 
-    `s_used`: optional 1-element int32 CUDA tensor holding the live cache
-    length when k/v are larger preallocated buffers — read in-kernel, so
-    the launch replays correctly from a hipGraph as the cache grows."""
+    `s_used`: optional int32 CUDA tensor holding the live cache length when
+    k/v are larger preallocated buffers: 1 element for the whole batch, or B
+    elements for one length per sequence (S above is then per sequence) —
+    read in-kernel, so the launch replays correctly from a hipGraph as the
+    cache grows."""
     if slopes is None:
         slopes = torch.zeros(q.shape[1], dtype=torch.float32, device=q.device)
     if s_used is None:
@@ -341,6 +343,29 @@ def attention_decode(
     return hip_ops().attn_decode(
         q.contiguous(), k.contiguous(), v.contiguous(), slopes, s_used
     )
+
+
+def attention_decode_append(
+    qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+    num_head: int, slopes: Optional[torch.Tensor], lens: torch.Tensor,
+) -> torch.Tensor:
+    """One decode step straight from the fused projection: qkv (B,1,3C),
+    k_cache/v_cache (B,H,S_alloc,D) of qkv's dtype -> (B,1,C).
+
+    `lens`: (B,) int32 on qkv's device, each sequence's length INCLUDING
+    the new token. The new k/v row is written into the caches in place at
+    row lens[b]-1 and sequence b attends over rows [0, lens[b]) with the
+    ALiBi bias slope*(j - (lens[b]-1)). On GPU one kernel pair does the
+    append and the attention (ops/csrc/attn_decode.hip; no q copy, no
+    index_copy_), graph-replayable as `lens` advances on device. CPU
+    tensors take the fp32 reference. Inference only (no autograd)."""
+    if not qkv.is_cuda:
+        return reference.attention_decode_append(
+            qkv, k_cache, v_cache, num_head, slopes, lens)
+    assert k_cache.shape[1] == num_head, "k_cache heads != num_head"
+    if slopes is None:
+        slopes = torch.zeros(num_head, dtype=torch.float32, device=qkv.device)
+    return hip_ops().attn_decode_append(qkv, k_cache, v_cache, slopes, lens)
 
 
 # ---------------------------------------------------------------------------

@@ -22,6 +22,9 @@ at::Tensor residual_dropout_fwd(at::Tensor x, at::Tensor h, double p, int64_t se
 at::Tensor residual_dropout_bwd(at::Tensor dy, double p, int64_t seed);
 at::Tensor attn_decode(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor slopes,
                        at::Tensor s_used);
+at::Tensor attn_decode_append(at::Tensor qkv, at::Tensor k_cache,
+                              at::Tensor v_cache, at::Tensor slopes,
+                              at::Tensor lens);
 std::vector<at::Tensor> attn_fwd(at::Tensor qkv, at::Tensor slopes, int64_t H,
                                  double p_drop, int64_t seed);
 std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor qkv, at::Tensor slopes,
@@ -43,6 +46,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("residual_dropout_fwd", &residual_dropout_fwd, "fused x + dropout(h) fwd (gfx950)");
   m.def("residual_dropout_bwd", &residual_dropout_bwd, "fused x + dropout(h) bwd (gfx950)");
   m.def("attn_decode", &attn_decode, "single-token KV-cache ALiBi attention (gfx950)");
+  m.def("attn_decode_append", &attn_decode_append,
+        "decode attention on the fused qkv row with per-sequence lengths; "
+        "appends the new K/V row to the caches in place (gfx950)");
   m.def("attn_fwd", &attn_fwd, "fused causal ALiBi flash attention fwd (gfx950 MFMA)");
   // fused: -1 = process default (ZTA_BWD_FUSED), 0 = two-kernel dq + dkdv,
   // 1 = single fused kernel (head_dim 128; other dims take the two-kernel path)

@@ -73,6 +73,47 @@ def attention(
     return out.to(q.dtype)
 
 
+def attention_decode_append(
+    qkv: torch.Tensor,
+    k_cache: torch.Tensor,
+    v_cache: torch.Tensor,
+    num_head: int,
+    slopes: Optional[torch.Tensor],
+    lens: torch.Tensor,
+) -> torch.Tensor:
+    """One decode step on the fused projection, one sequence at a time.
+
+    qkv: (B, 1, 3C); k_cache / v_cache: (B, H, S_alloc, D), written in place
+    at row lens[b] - 1 with the new k / v; lens: (B,) int32 INCLUDING the new
+    token. Sequence b attends over its rows [0, lens[b]) with the ALiBi bias
+    slope_h * (j - (lens[b] - 1)); rows >= lens[b] are never read. fp32
+    softmax; returns (B, 1, C) in qkv.dtype. lens[b] == 0 writes nothing and
+    returns zeros for that row.
+    """
+    B, _, C3 = qkv.shape
+    C = C3 // 3
+    H = num_head
+    D = C // H
+    S_alloc = k_cache.shape[2]
+    q, k_new, v_new = (t.reshape(B, H, D) for t in qkv.split(C, dim=-1))
+    out = torch.zeros(B, H, D, dtype=torch.float32, device=qkv.device)
+    for b, S in enumerate(lens.tolist()):
+        S = min(max(int(S), 0), S_alloc)
+        if S == 0:
+            continue
+        k_cache[b, :, S - 1] = k_new[b].to(k_cache.dtype)
+        v_cache[b, :, S - 1] = v_new[b].to(v_cache.dtype)
+        k = k_cache[b, :, :S].float()  # (H, S, D)
+        v = v_cache[b, :, :S].float()
+        scores = (k @ q[b].float().unsqueeze(-1)).squeeze(-1) / math.sqrt(D)
+        if slopes is not None:
+            pos = torch.arange(S, device=qkv.device, dtype=torch.float32) - (S - 1)
+            scores = scores + slopes.to(qkv.device).float().view(H, 1) * pos
+        probs = F.softmax(scores, dim=-1)  # (H, S)
+        out[b] = (probs.unsqueeze(1) @ v).squeeze(1)
+    return out.reshape(B, 1, C).to(qkv.dtype)
+
+
 def drop_mask(seed: int, B: int, H: int, T: int, p: float) -> torch.Tensor:
     """Regenerate the attention-dropout keep mask of the HIP kernels.
 
