@@ -7,7 +7,8 @@ Two modes:
           POST /generate {"prompt": ..., "max_new_tokens": ..., ...}
           (FastAPI + uvicorn instead of the reference's Gradio UI — same
           streaming KV-cached generation + samplers, reference app.py:42-142.)
-          POST /generate_batch {"prompts": [...], ...same options...}
+          POST /generate_batch {"prompts": [...], ...same options...,
+                                "prefill_chunk": P (optional)}
             -> {"completions": [...]}: prompts of any lengths, one batch
   Several --prompt flags on the CLI go through the same batched path and
   print one completion per line.
@@ -85,6 +86,8 @@ def _options(req: dict) -> dict:
         top_p=float(req.get("top_p", 0.95)),
         repetition_penalty=float(req.get("repetition_penalty", 1.1)),
         sample=not bool(req.get("greedy", False)),
+        prefill_chunk=(int(req["prefill_chunk"])
+                       if req.get("prefill_chunk") is not None else None),
     )
 
 
@@ -101,6 +104,9 @@ def main():
     p.add_argument("--top-p", type=float, default=0.95)
     p.add_argument("--repetition-penalty", type=float, default=1.1)
     p.add_argument("--greedy", action="store_true")
+    p.add_argument("--prefill-chunk", type=int, default=None,
+                   help="send the prompt through the prefill in slices of this "
+                   "many positions (bounds activation memory of long prompts)")
     p.add_argument("--serve", action="store_true")
     p.add_argument("--port", type=int, default=7860)
     p.add_argument(
@@ -121,6 +127,7 @@ def main():
         top_p=args.top_p,
         repetition_penalty=args.repetition_penalty,
         sample=not args.greedy,
+        prefill_chunk=args.prefill_chunk,
     )
 
     if args.serve:

@@ -97,6 +97,14 @@ class InferenceAttention(nn.Module):
         self._qkv_w = None
         super()._load_from_state_dict(*args, **kwargs)
 
+    def _fused_qkv_w(self, dtype) -> torch.Tensor:
+        """The (3C, C) q|k|v weight, materialized lazily."""
+        if getattr(self, "_qkv_w", None) is None or self._qkv_w.dtype != dtype:
+            self._qkv_w = torch.cat(
+                [self.query.weight, self.key.weight, self.value.weight], dim=0
+            ).contiguous()
+        return self._qkv_w
+
     def forward(
         self,
         x: torch.Tensor,
@@ -111,11 +119,7 @@ class InferenceAttention(nn.Module):
             # decode: one fused (3C, C) GEMV instead of three launches (the
             # fused weight is materialized lazily; same total weight-stream
             # bytes, 1/3 the kernel launches and a fuller grid)
-            if getattr(self, "_qkv_w", None) is None or self._qkv_w.dtype != x.dtype:
-                self._qkv_w = torch.cat(
-                    [self.query.weight, self.key.weight, self.value.weight], dim=0
-                ).contiguous()
-            qkv = ops.decode_linear(x, self._qkv_w)
+            qkv = ops.decode_linear(x, self._fused_qkv_w(x.dtype))
             if static_cache is not None:
                 # the kernel reads q / k / v straight from the projection
                 # row, appends k / v at device position len-1 (len already
@@ -170,6 +174,18 @@ class InferenceAttention(nn.Module):
                 out = F.scaled_dot_product_attention(q, k, v, attn_mask=causal.view(1, 1, T, Tk))
         out = out.transpose(1, 2).reshape(B, T, C)
         return _proj(out, self.fc_resid.weight), present
+
+    def prefill(self, x: torch.Tensor, cache: "StaticKVCache", layer_idx: int,
+                lens: torch.Tensor, start: torch.Tensor) -> torch.Tensor:
+        """Prompt rows (or one chunk of them) through the native prefill
+        kernel: one fused qkv GEMM, ops.attention_prefill_append (fills cache
+        rows start[b]..start[b]+lens[b] and attends over the cache; no mask
+        tensor, no index_copy_), the output projection."""
+        qkv = F.linear(x, self._fused_qkv_w(x.dtype))
+        out = ops.attention_prefill_append(
+            qkv, cache.k[layer_idx], cache.v[layer_idx], self.num_head,
+            self.slopes, lens, start)
+        return F.linear(out, self.fc_resid.weight)
 
 
 class InferenceMLP(nn.Module):
@@ -282,6 +298,58 @@ class GPT2(nn.Module):
         return _proj(ln_x, self.lm_head.weight)
 
     @torch.no_grad()
+    def prefill(
+        self,
+        idx: torch.Tensor,
+        cache: StaticKVCache,
+        lens=None,
+        chunk: Optional[int] = None,
+    ) -> torch.Tensor:
+        """Fill `cache` from the prompts and return each sequence's
+        last-token logits, (B, V).
+
+        idx: (B, T) right-padded prompts; lens: one length per sequence (a
+        sequence or a (B,) tensor; None: all T). Per layer: one fused qkv
+        GEMM, ops.attention_prefill_append, the output projection, the MLP.
+        Pad rows are never written to the cache and attend to nothing. Each
+        sequence's last hidden row is gathered on device before the final
+        norm, so norm and lm_head run on (B, 1, C).
+
+        chunk=P sends the prompt through in slices of P positions (slice c
+        holds lens_c = clamp(lens - cP, 0, P) new rows behind
+        start_c = min(lens, cP) cached ones), which bounds the activation
+        memory of a long prompt; the result is the unchunked one up to
+        rounding. `cache.len_t` is left to the caller. A one-token prompt
+        goes through the decode step, which appends at row len_t - 1.
+        """
+        B, T = idx.shape
+        if T == 1:
+            return self(idx, static_cache=cache)[:, -1]
+        dev = idx.device
+        if lens is None:
+            lens_t = torch.full((B,), T, dtype=torch.int32, device=dev)
+        else:
+            lens_t = torch.as_tensor(lens, dtype=torch.int32).to(dev)
+        P = T if not chunk else max(1, min(int(chunk), T))
+        rows = torch.arange(B, device=dev)
+        last = None
+        for c0 in range(0, T, P):
+            x = self.wte(idx[:, c0:c0 + P])
+            Pc = x.shape[1]
+            lens_c = (lens_t - c0).clamp(0, Pc)
+            start_c = lens_t.clamp(max=c0)
+            for i, block in enumerate(self.blocks):
+                x = x + block.attn.prefill(block.ln1(x), cache, i, lens_c, start_c)
+                x = x + block.mlp(block.ln2(x))
+            # the slice that holds row lens - 1 supplies it (device select)
+            pos = lens_t.long() - 1 - c0
+            here = (pos >= 0) & (pos < Pc)
+            row = x[rows, pos.clamp(0, Pc - 1)]  # (B, C)
+            last = row if last is None else torch.where(here.view(B, 1), row, last)
+        x = self.norm(last.unsqueeze(1))
+        return _proj(x, self.lm_head.weight)[:, 0]
+
+    @torch.no_grad()
     def generate(
         self,
         idx: torch.Tensor,
@@ -340,10 +408,12 @@ def generate_fast(
     idx: torch.Tensor,
     max_new_tokens: int,
     use_graph: bool = True,
+    prefill_chunk: Optional[int] = None,
 ) -> torch.Tensor:
     """Greedy generation with a static KV cache and (optionally) the whole
     per-token decode step captured in a hipGraph — removes the per-layer
-    Python/launch overhead that dominates single-token latency.
+    Python/launch overhead that dominates single-token latency. The prompt
+    goes through GPT2.prefill, in slices of `prefill_chunk` positions if set.
     """
     B, T0 = idx.shape
     dev = idx.device
@@ -359,8 +429,8 @@ def generate_fast(
     # prefill. The length goes first: a one-token prompt prefills through
     # the decode step, which appends at row len - 1 (T0 > 1 never reads it)
     cache.set_len(T0)
-    logits = model(idx, static_cache=cache)
-    cur = logits[:, -1:].argmax(-1)  # (B, 1) — static input buffer
+    last = model.prefill(idx, cache, chunk=prefill_chunk)
+    cur = last.argmax(-1, keepdim=True)  # (B, 1) — static input buffer
     out_tokens = [cur.clone()]
 
     def step():
@@ -397,6 +467,7 @@ def generate_batch(
     top_p: float = 1.0,
     repetition_penalty: float = 1.0,
     use_graph: bool = True,
+    prefill_chunk: Optional[int] = None,
 ) -> List[List[int]]:
     """Batched generation for prompts of DIFFERENT lengths (each >= 1 and
     <= model.num_ctx), on the model's device.
@@ -406,10 +477,10 @@ def generate_batch(
     min(max_new_tokens, num_ctx - len(prompts[b])) tokens — generate_fast's
     rule per sequence.
 
-    One right-padded prefill fills the static cache: ALiBi's bias depends
-    only on j - i and the pad keys lie in every real token's future, so the
-    real rows are exact; pad K/V land in rows >= len(prompts[b]), which the
-    decode kernel never reads and later tokens overwrite. Decode then runs
+    One right-padded GPT2.prefill with the per-sequence lengths fills the
+    static cache (in slices of `prefill_chunk` positions if set): the pad
+    rows attend to nothing and are never written to the cache, and only each
+    sequence's last row reaches the lm_head. Decode then runs
     with per-sequence lengths (StaticKVCache.len_t), sampling batched and on
     device (no per-token host sync). Finished rows stop advancing, keep
     being fed their last token and their outputs are discarded.
@@ -445,8 +516,7 @@ def generate_batch(
 
     # lengths first: prompts of one token prefill through the decode step
     cache.set_len(lens_t)
-    logits = model(idx, static_cache=cache)
-    last = logits[torch.arange(B, device=dev), lens_t.long() - 1]  # (B, V)
+    last = model.prefill(idx, cache, lens_t, chunk=prefill_chunk)  # (B, V)
 
     cur = idx.new_zeros((B, 1))  # static input buffers of the decode step
     active = torch.ones(B, dtype=torch.int32, device=dev)

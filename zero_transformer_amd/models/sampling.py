@@ -101,14 +101,16 @@ def generate_stream(
     sample: bool = True,
     eos_token: Optional[int] = None,
     use_graph: bool = True,
+    prefill_chunk: Optional[int] = None,
 ) -> Iterator[int]:
     """Streaming generation with KV cache (reference app.py:42-94).
 
     On GPU the decode step runs against a static KV cache with the whole
     per-token model call captured in a hipGraph (the generate_fast
     machinery) — sampling stays host-side between replays, so every
-    sampler/penalty option streams at graph-replay latency. CPU keeps the
-    dynamic layer_past path.
+    sampler/penalty option streams at graph-replay latency; the prompt goes
+    through GPT2.prefill (in slices of `prefill_chunk` positions if set).
+    CPU keeps the dynamic layer_past path.
     """
     model.eval()
     assert idx.shape[0] == 1, "generate_stream streams a single prompt (B=1); use inference.generate_batch for batched decoding"
@@ -131,7 +133,7 @@ def generate_stream(
         # length first: a one-token prompt prefills through the decode
         # step, which appends at row len - 1 (T0 > 1 never reads it)
         cache.set_len(T0)
-        logits = model(idx, static_cache=cache)
+        logits = model.prefill(idx, cache, chunk=prefill_chunk).unsqueeze(1)
         cur = idx.new_zeros((B, 1))
 
         def step():

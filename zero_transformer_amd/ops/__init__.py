@@ -368,6 +368,49 @@ def attention_decode_append(
     return hip_ops().attn_decode_append(qkv, k_cache, v_cache, slopes, lens)
 
 
+def attention_prefill_append(
+    qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+    num_head: int, slopes: Optional[torch.Tensor],
+    lens: Optional[torch.Tensor] = None,
+    start: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """Prefill, or one chunk of it, straight from the fused projection: qkv
+    (B,T,3C), k_cache/v_cache (B,H,S_alloc,D) of qkv's dtype -> (B,T,C).
+
+    `lens`, `start`: (B,) int32 on qkv's device. lens[b] is the number of new
+    rows of sequence b, start[b] the number of rows already in its cache;
+    None means every row is new / nothing is cached. With start clamped to
+    [0, S_alloc] and n = clamp(lens[b], 0, min(T, S_alloc - start[b])), the
+    k/v columns of rows i < n are written into the caches in place at rows
+    start[b]+i (no other row is touched, pad rows are never written), query
+    row i < n attends over cache rows [0, start[b]+i] with the ALiBi bias
+    slope*(j - (start[b]+i)), and rows i >= n of the result are zeros. On GPU
+    (fp16/bf16, head_dim 32/64/96/128) one kernel pair does the cache fill
+    and a flash attention that stages K/V from the cache
+    (ops/csrc/attn_prefill.hip; no mask tensor, no index_copy_, no host
+    sync, deterministic). CPU tensors, fp32 and other head dims take the fp32
+    reference. Inference only (no autograd)."""
+    D = k_cache.shape[3]
+    if not (
+        qkv.is_cuda
+        and qkv.dtype in (torch.float16, torch.bfloat16)
+        and D in (32, 64, 96, 128)
+    ):
+        return reference.attention_prefill_append(
+            qkv, k_cache, v_cache, num_head, slopes, lens, start)
+    assert k_cache.shape[1] == num_head, "k_cache heads != num_head"
+    B, T = qkv.shape[:2]
+    if slopes is None:
+        slopes = torch.zeros(num_head, dtype=torch.float32, device=qkv.device)
+    # None takes the kernel's one code path with the explicit full tensors
+    if lens is None:
+        lens = torch.full((B,), T, dtype=torch.int32, device=qkv.device)
+    if start is None:
+        start = torch.zeros(B, dtype=torch.int32, device=qkv.device)
+    return hip_ops().attn_prefill_append(
+        qkv.contiguous(), k_cache, v_cache, slopes, lens, start)
+
+
 # ---------------------------------------------------------------------------
 # Fused residual-add + dropout:  y = x + dropout(h, p)
 # ---------------------------------------------------------------------------

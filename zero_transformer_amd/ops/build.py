@@ -29,6 +29,7 @@ SOURCES = [
     "residual.hip",
     "attention_fwd.hip",
     "attn_decode.hip",
+    "attn_prefill.hip",
     "attention_bwd.hip",
     "gemm_lt.hip",
     "gemv.hip",

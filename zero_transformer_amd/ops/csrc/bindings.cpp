@@ -25,6 +25,9 @@ at::Tensor attn_decode(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor slop
 at::Tensor attn_decode_append(at::Tensor qkv, at::Tensor k_cache,
                               at::Tensor v_cache, at::Tensor slopes,
                               at::Tensor lens);
+at::Tensor attn_prefill_append(at::Tensor qkv, at::Tensor k_cache,
+                               at::Tensor v_cache, at::Tensor slopes,
+                               at::Tensor lens, at::Tensor start);
 std::vector<at::Tensor> attn_fwd(at::Tensor qkv, at::Tensor slopes, int64_t H,
                                  double p_drop, int64_t seed);
 std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor qkv, at::Tensor slopes,
@@ -49,6 +52,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_decode_append", &attn_decode_append,
         "decode attention on the fused qkv row with per-sequence lengths; "
         "appends the new K/V row to the caches in place (gfx950)");
+  m.def("attn_prefill_append", &attn_prefill_append,
+        "prefill attention on the fused qkv rows against the KV cache, with "
+        "per-sequence new-row counts and cached-row offsets; fills the caches "
+        "in place (gfx950 MFMA)");
   m.def("attn_fwd", &attn_fwd, "fused causal ALiBi flash attention fwd (gfx950 MFMA)");
   // fused: -1 = process default (ZTA_BWD_FUSED), 0 = two-kernel dq + dkdv,
   // 1 = single fused kernel (head_dim 128; other dims take the two-kernel path)

@@ -114,6 +114,62 @@ def attention_decode_append(
     return out.reshape(B, 1, C).to(qkv.dtype)
 
 
+def attention_prefill_append(
+    qkv: torch.Tensor,
+    k_cache: torch.Tensor,
+    v_cache: torch.Tensor,
+    num_head: int,
+    slopes: Optional[torch.Tensor],
+    lens: Optional[torch.Tensor] = None,
+    start: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """Prefill (or one chunk of it) on the fused projection, one sequence at
+    a time.
+
+    qkv: (B, T, 3C); k_cache / v_cache: (B, H, S_alloc, D), written in place.
+    lens[b] is the number of new rows of sequence b, start[b] the number of
+    rows already in its cache (None: every row is new / nothing is cached).
+    With st = clamp(start[b], 0, S_alloc) and
+    n = clamp(lens[b], 0, min(T, S_alloc - st)), the k / v columns of rows
+    i < n go to cache rows st + i and no other cache row is touched; query row
+    i < n sits at position st + i and attends over cache rows [0, st + i]
+    with the ALiBi bias slope_h * (j - (st + i)). fp32 softmax; returns
+    (B, T, C) in qkv.dtype with rows i >= n zero. Rows >= n of qkv and cache
+    rows >= st + n are never read.
+    """
+    B, T, C3 = qkv.shape
+    C = C3 // 3
+    H = num_head
+    D = C // H
+    S_alloc = k_cache.shape[2]
+    lens_l = [T] * B if lens is None else lens.tolist()
+    start_l = [0] * B if start is None else start.tolist()
+    out = torch.zeros(B, T, C, dtype=torch.float32, device=qkv.device)
+    for b in range(B):
+        st = min(max(int(start_l[b]), 0), S_alloc)
+        n = min(max(int(lens_l[b]), 0), min(T, S_alloc - st))
+        if n == 0:
+            continue
+        q, k_new, v_new = (
+            t.reshape(n, H, D).transpose(0, 1) for t in qkv[b, :n].split(C, dim=-1)
+        )  # (H, n, D)
+        k_cache[b, :, st:st + n] = k_new.to(k_cache.dtype)
+        v_cache[b, :, st:st + n] = v_new.to(v_cache.dtype)
+        S = st + n
+        k = k_cache[b, :, :S].float()  # (H, S, D)
+        v = v_cache[b, :, :S].float()
+        scores = (q.float() @ k.transpose(-1, -2)) / math.sqrt(D)  # (H, n, S)
+        qpos = torch.arange(st, S, device=qkv.device, dtype=torch.float32)
+        kpos = torch.arange(S, device=qkv.device, dtype=torch.float32)
+        rel = kpos.view(1, S) - qpos.view(n, 1)  # j - (st + i)
+        if slopes is not None:
+            scores = scores + slopes.to(qkv.device).float().view(H, 1, 1) * rel
+        scores = scores.masked_fill(rel > 0, torch.finfo(torch.float32).min)
+        probs = F.softmax(scores, dim=-1)
+        out[b, :n] = (probs @ v).transpose(0, 1).reshape(n, C)
+    return out.to(qkv.dtype)
+
+
 def drop_mask(seed: int, B: int, H: int, T: int, p: float) -> torch.Tensor:
     """Regenerate the attention-dropout keep mask of the HIP kernels.
 
