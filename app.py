@@ -12,6 +12,13 @@ Two modes:
             -> {"completions": [...]}: prompts of any lengths, one batch
   Several --prompt flags on the CLI go through the same batched path and
   print one completion per line.
+  Paged:  python app.py ... --serve --paged --slots 16 --kv-pages 512
+          POST /submit {"prompt": ..., "max_new_tokens": ...} -> {"completion": ...}
+          One engine thread (models/paged.py ServingEngine: paged KV cache,
+          continuous batching, prefix reuse) serves every /submit: a request
+          joins the running batch and its call returns when it is done. The
+          sampling options are the server's (the command line's), not the
+          request's.
 
 Tokenizer: GPT-NeoX-20B via transformers when its assets are cached locally
 (reference app.py:27); otherwise a byte-level fallback so the app works on
@@ -77,6 +84,98 @@ def generate_texts(model, tok, prompts, **kw) -> list:
     return [tok.decode(o) for o in outs]
 
 
+class EngineWorker:
+    """One thread that owns a ServingEngine: submit() may be called from any
+    thread, queues the request and blocks until its tokens are ready. The
+    thread sleeps on the queue while the engine is idle."""
+
+    def __init__(self, engine):
+        import queue
+        import threading
+
+        self.engine = engine
+        self.inbox = queue.Queue()
+        self.pending = {}  # request id -> (event, result holder)
+        self.failed = None  # what ended the thread, if anything did
+        self.thread = threading.Thread(target=self._loop, daemon=True)
+        self.thread.start()
+
+    def submit(self, tokens, max_new_tokens: int) -> list:
+        import threading
+
+        done, box = threading.Event(), {}
+        self.inbox.put((tokens, max_new_tokens, done, box))
+        # a timed wait: a request queued after the thread has died is caught
+        # here, not by the thread's own clean-up
+        while not done.wait(0.5):
+            if self.failed is not None:
+                self._fail(self.failed)
+        if "error" in box:
+            raise box["error"]
+        return box["tokens"]
+
+    def _take(self, item) -> None:
+        tokens, n, done, box = item
+        try:
+            self.pending[self.engine.submit(tokens, n)] = (done, box)
+        except ValueError as e:  # a request that can never fit
+            box["error"] = e
+            done.set()
+
+    def _loop(self) -> None:
+        try:
+            self._serve()
+        except BaseException as e:  # the engine is gone: nobody may wait for it
+            self.failed = e
+            self._fail(e)
+            raise
+
+    def _fail(self, err) -> None:
+        """Hand `err` to every caller that waits or is queued."""
+        import queue
+
+        waiting = list(self.pending.values())
+        self.pending.clear()
+        try:
+            while True:
+                item = self.inbox.get_nowait()
+                if item is not None:
+                    waiting.append(item[2:])
+        except queue.Empty:
+            pass
+        for done, box in waiting:
+            box["error"] = RuntimeError(f"the serving engine stopped: {err!r}")
+            done.set()
+
+    def _serve(self) -> None:
+        import queue
+
+        while True:
+            if self.engine.idle() and not self.pending:
+                item = self.inbox.get()
+                if item is None:
+                    return
+                self._take(item)
+            try:
+                while True:
+                    item = self.inbox.get_nowait()
+                    if item is None:
+                        return
+                    self._take(item)
+            except queue.Empty:
+                pass
+            if not self.engine.idle():
+                self.engine.step()
+            for rid, toks in self.engine.poll().items():
+                done, box = self.pending.pop(rid)
+                box["tokens"] = toks
+                done.set()
+
+    def close(self) -> None:
+        self.inbox.put(None)
+        self.thread.join()
+
+
 def _options(req: dict) -> dict:
     """Sampling options of a request body, with the server defaults."""
     return dict(
@@ -107,6 +206,13 @@ def main():
     p.add_argument("--prefill-chunk", type=int, default=None,
                    help="send the prompt through the prefill in slices of this "
                    "many positions (bounds activation memory of long prompts)")
+    p.add_argument("--paged", action="store_true",
+                   help="with --serve: POST /submit through one continuous-"
+                   "batching engine over a paged KV cache")
+    p.add_argument("--slots", type=int, default=16,
+                   help="--paged: sequences decoded per step")
+    p.add_argument("--kv-pages", type=int, default=256,
+                   help="--paged: pages of 64 rows in the KV pool (page 0 is reserved)")
     p.add_argument("--serve", action="store_true")
     p.add_argument("--port", type=int, default=7860)
     p.add_argument(
@@ -133,7 +239,14 @@ def main():
     if args.serve:
         import uvicorn
 
-        app = build_app(model, tok, device)
+        engine = None
+        if args.paged:
+            from zero_transformer_amd.models.paged import ServingEngine
+
+            opts = {k: v for k, v in kw.items() if k != "max_new_tokens"}
+            engine = ServingEngine(model, args.slots, args.kv_pages,
+                                   eos_token=getattr(tok, "eos_token_id", None), **opts)
+        app = build_app(model, tok, device, engine)
         uvicorn.run(app, host=args.host, port=args.port)
     else:
         prompts = args.prompt or ["Hello"]
@@ -144,12 +257,29 @@ def main():
                 print((prompt + text).replace("\n", "\\n"))
 
 
-def build_app(model, tok, device):
+def build_app(model, tok, device, engine=None):
     """FastAPI app over a loaded model (split out of main() so the server
-    surface is unit-testable with fastapi.testclient)."""
-    from fastapi import Body, FastAPI
+    surface is unit-testable with fastapi.testclient). With a ServingEngine,
+    POST /submit is served by one engine thread."""
+    from fastapi import Body, FastAPI, HTTPException
 
     app = FastAPI(title="zero_transformer_amd inference")
+
+    if engine is not None:
+        worker = EngineWorker(engine)
+        app.state.worker = worker
+
+        @app.post("/submit")
+        def submit(req: dict = Body(...)):
+            # a sync endpoint: each call waits in its own server thread
+            try:
+                toks = worker.submit(tok.encode(str(req["prompt"])),
+                                     int(req.get("max_new_tokens", 128)))
+            except ValueError as e:
+                raise HTTPException(status_code=400, detail=str(e))
+            except RuntimeError as e:
+                raise HTTPException(status_code=503, detail=str(e))
+            return {"completion": tok.decode(toks)}
 
     @app.post("/generate")
     def generate(req: dict = Body(...)):

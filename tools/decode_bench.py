@@ -3,9 +3,20 @@
     python tools/decode_bench.py --model-size 1_3b --tokens 128 --batch 1
     python tools/decode_bench.py --model-size 1_3b --batch 16 --fast --ragged
     python tools/decode_bench.py --model-size 1_3b --prefill --prompt-len 1024
+    python tools/decode_bench.py --model-size 1_3b --batch 16 --fast --paged
+    python tools/decode_bench.py --model-size 1_3b --batch 16 --stream 64
+    python tools/decode_bench.py --model-size 1_3b --batch 16 --stream 64 --prefix-len 512
+
+--paged runs the same workload through the paged KV cache (models/paged.py):
+--fast [--ragged] through a ServingEngine with --batch slots, --prefill through
+GPT2.prefill on a PagedKVCache. --stream N is the serving scenario: N seeded
+requests (prompts of 54..119 tokens, 16..256 new tokens each) through an
+engine with --batch slots, against generate_batch over the same requests in
+arrival-order groups of --batch.
 """
 
 import argparse
+import gc
 import os
 import statistics
 import sys
@@ -40,12 +51,28 @@ def main():
                    "and the SDPA static-cache forward it replaced, alternating, "
                    "median of --runs; with --ragged the --ragged lengths, "
                    "right-padded")
+    p.add_argument("--paged", action="store_true",
+                   help="with --fast / --prefill: the paged KV cache instead of "
+                   "the static one (pages of 64 rows)")
+    p.add_argument("--step", action="store_true",
+                   help="time the captured decode step alone, static cache against "
+                   "paged cache, alternating in one process: --tokens replays from "
+                   "--prompt-len cached rows, median of --runs rounds")
+    p.add_argument("--stream", type=int, default=0,
+                   help="serving scenario with this many requests: engine with "
+                   "--batch slots against generate_batch in groups of --batch")
+    p.add_argument("--prefix-len", type=int, default=0,
+                   help="with --stream: every prompt starts with the same "
+                   "this-many tokens; the engine runs with and without prefix reuse")
+    p.add_argument("--kv-pages", type=int, default=0,
+                   help="pages in the pool (0: what --batch full-length requests need)")
     p.add_argument("--prefill-chunk", type=int, default=None)
     p.add_argument("--runs", type=int, default=15)
     args = p.parse_args()
-    args.fast = args.fast or args.prefill
+    args.fast = args.fast or args.prefill or bool(args.stream) or args.step
     assert args.fast or not args.ragged, "--ragged goes with --fast"
     assert args.ragged or not args.sequential, "--sequential goes with --ragged"
+    assert args.fast or not args.paged, "--paged goes with --fast, --prefill or --stream"
     gemm_tune.enable()  # committed hipBLASLt tunings (incl. decode shapes)
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
@@ -98,6 +125,39 @@ def main():
             # per-sequence rate, like the other modes: x batch below
             return n / args.batch / (time.perf_counter() - t0)
 
+    if args.stream:
+        return bench_stream(args, model)
+    if args.step:
+        return bench_step(args, model)
+
+    if args.paged:
+        from zero_transformer_amd.models.paged import ServingEngine
+
+        if not args.ragged:
+            prompts = idx.tolist()
+        rows = max(len(pr) for pr in prompts) + args.tokens
+        pages = args.kv_pages or args.batch * -(-min(rows, model.num_ctx) // 64) + 1
+        reuse = []
+
+        @torch.no_grad()
+        def run():
+            # like generate_fast / generate_batch, a call pays for its cache
+            # and its graph capture; the second figure reuses the engine
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            eng = ServingEngine(model, args.batch, pages, prefix_cache=False)
+            for pr in prompts:
+                eng.submit(pr, args.tokens)
+            n = sum(len(r) for r in eng.run().values())
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            for pr in prompts:
+                eng.submit(pr, args.tokens)
+            n2 = sum(len(r) for r in eng.run().values())
+            torch.cuda.synchronize()
+            reuse.append(n2 / (time.perf_counter() - t1))
+            return n / args.batch / (t1 - t0)
+
     if args.prefill:
         return bench_prefill(args, model, idx, lens if args.ragged else None)
 
@@ -107,8 +167,145 @@ def main():
     if args.ragged:
         mode = (f"ragged {min(lens)}..{max(lens)} "
                 + ("sequential" if args.sequential else "batched"))
+    if args.paged:
+        mode = "paged " + mode.replace("fast(graph)", "engine(graph)")
     print(f"{args.model_size} {args.dtype} batch {args.batch} {mode}: "
-          f"{tps * args.batch:.1f} tokens/s ({1e3 / tps:.2f} ms/token)")
+          f"{tps * args.batch:.1f} tokens/s ({1e3 / tps:.2f} ms/token)"
+          + (f"; engine reused {reuse[-1]:.1f} tokens/s" if args.paged else ""))
+
+
+@torch.no_grad()
+def bench_step(args, model):
+    """The captured decode step alone (no sampling, no prefill, no capture in
+    the timed window): every sequence starts at --prompt-len cached rows and
+    grows by one per replay, --tokens replays per round."""
+    from zero_transformer_amd.models.inference import (GRAPH_SCRATCH_ROWS, StaticKVCache,
+                                                       capture_decode_step)
+    from zero_transformer_amd.models.paged import PagedKVCache
+
+    B, T0, n = args.batch, args.prompt_len, args.tokens
+    dev = next(model.parameters()).device
+    attn = model.blocks[0].attn
+    rows = T0 + n + GRAPH_SCRATCH_ROWS
+    per = -(-rows // 64)
+    geom = (model.N, B, attn.num_head, attn.head_dim)
+    dtype = next(model.parameters()).dtype
+    caches = {"contiguous": StaticKVCache(*geom, rows, dev, dtype),
+              "paged": PagedKVCache(*geom, B * per + 1, 64, per, dev, dtype)}
+    for b in range(B):
+        caches["paged"].assign(b, rows)
+    cur = torch.zeros(B, 1, dtype=torch.long, device=dev)
+    one = torch.ones(B, dtype=torch.int32, device=dev)
+    graphs = {}
+    for name, cache in caches.items():
+        cache.set_len(T0)
+
+        def step(cache=cache):
+            cache.advance(one)
+            return model(cur, static_cache=cache)
+
+        graphs[name], _ = capture_decode_step(step, cache, T0)
+    times = {name: [] for name in graphs}
+    for r in range(2 + args.runs):
+        for name, graph in graphs.items():
+            caches[name].set_len(T0)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(n):
+                graph.replay()
+            torch.cuda.synchronize()
+            if r >= 2:
+                times[name].append((time.perf_counter() - t0) / n * 1e6)
+    med = {k: statistics.median(v) for k, v in times.items()}
+    print(f"{args.model_size} {args.dtype} decode step batch {B}, rows {T0}..{T0 + n}: "
+          + ", ".join(f"{k} {med[k]:.1f} us (min {min(times[k]):.1f}, max {max(times[k]):.1f})"
+                      for k in med)
+          + f", paged / contiguous {med['paged'] / med['contiguous']:.4f}")
+
+
+@torch.no_grad()
+def bench_stream(args, model):
+    """The serving scenario; greedy, no EOS, so both sides emit exactly the
+    requested tokens and only those are counted."""
+    from zero_transformer_amd.models.inference import GRAPH_SCRATCH_ROWS, generate_batch
+    from zero_transformer_amd.models.paged import ServingEngine
+
+    g = torch.Generator().manual_seed(0)
+    N, S = args.stream, args.batch
+    lens = torch.randint(54, 120, (N,), generator=g).tolist()
+    news = torch.randint(16, 257, (N,), generator=g).tolist()
+    prefix = torch.randint(0, model.vocab_size, (args.prefix_len,), generator=g).tolist()
+    prompts = [prefix + torch.randint(0, model.vocab_size, (n,), generator=g).tolist()
+               for n in lens]
+    limits = [min(m, model.num_ctx - len(p)) for p, m in zip(prompts, news)]
+    total = sum(limits)
+    attn = model.blocks[0].attn
+    row_bytes = 2 * model.N * attn.num_head * attn.head_dim * 2  # k + v, 16-bit
+    full = -(-min(model.num_ctx, max(len(p) + m for p, m in zip(prompts, limits))) // 64)
+    pages = args.kv_pages or S * full + 1
+
+    class TimedEngine(ServingEngine):
+        """Adds up the prefill time (a device sync on either side). A
+        subclass, not a wrapper stored on the instance: that would put the
+        engine, and its hipGraph, in a reference cycle, and a graph must not
+        be destroyed by the cycle collector while another one is captured."""
+        prefill_s = 0.0
+
+        def _prefill(self, batch):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            super()._prefill(batch)
+            torch.cuda.synchronize()
+            self.prefill_s += time.perf_counter() - t0
+
+    def sync_time(f):
+        gc.collect()  # never inside a capture (see TimedEngine)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = f()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    def static():
+        out, rows = [], 0
+        for i in range(0, N, S):
+            grp, lim = prompts[i:i + S], limits[i:i + S]
+            res = generate_batch(model, grp, max(lim))
+            out += [r[:m] for r, m in zip(res, lim)]
+            rows = max(rows, len(grp) * min(
+                model.num_ctx, max(len(p) + min(max(lim), model.num_ctx - len(p))
+                                   for p in grp) + GRAPH_SCRATCH_ROWS))
+        return out, rows
+
+    def engine(prefix_cache):
+        eng = TimedEngine(model, S, pages, prefix_cache=prefix_cache)
+        peak = 0
+        ids = [eng.submit(p, m) for p, m in zip(prompts, news)]
+        res = {}
+        while not eng.idle():
+            eng.step()
+            c = eng.cache
+            peak = max(peak, c.num_pages - 1 - c.pages_free() - c.pages_held())
+            res.update(eng.poll())
+        return [res[i] for i in ids], eng, peak
+
+    static()  # warm-up of both paths (GEMM tunings, allocator)
+    engine(True)
+    for _ in range(2):  # alternating, twice
+        dt, (out_s, rows) = sync_time(static)
+        assert sum(len(r) for r in out_s) == total
+        print(f"{args.model_size} {args.dtype} stream {N} x {S} static groups: "
+              f"{total / dt:.1f} tokens/s ({dt:.2f} s), KV {rows * row_bytes / 2**20:.0f} MiB")
+        for pc in ((True, False) if args.prefix_len else (True,)):
+            dt, (out_e, eng, peak) = sync_time(lambda: engine(pc))
+            assert sum(len(r) for r in out_e) == total
+            agree = sum(a == b for a, b in zip(out_e, out_s))
+            print(f"{args.model_size} {args.dtype} stream {N} x {S} engine "
+                  f"prefix_cache={pc}: {total / dt:.1f} tokens/s ({dt:.2f} s), "
+                  f"KV pool {eng.cache.kv_bytes() / 2**20:.0f} MiB ({pages} pages), "
+                  f"peak live pages {peak}, prefill {eng.prefill_s * 1e3:.0f} ms in "
+                  f"{eng.prefill_calls} calls, {eng.decode_steps} decode steps, "
+                  f"{agree}/{N} requests token-equal to static")
 
 
 @torch.no_grad()
@@ -134,6 +331,18 @@ def bench_prefill(args, model, idx, lens):
     def native():
         return model.prefill(idx, cache, lens_t, chunk=args.prefill_chunk)
 
+    if args.paged:
+        from zero_transformer_amd.models.paged import PagedKVCache
+
+        per = -(-T // 64)
+        pcache = PagedKVCache(model.N, B, attn.num_head, attn.head_dim, B * per + 1, 64,
+                              per, dev, next(model.parameters()).dtype)
+        for b in range(B):
+            pcache.assign(b, T)
+
+        def paged():
+            return model.prefill(idx, pcache, lens_t, chunk=args.prefill_chunk)
+
     def sdpa():
         return model(idx, static_cache=cache)[rows, lens_t.long() - 1]
 
@@ -144,9 +353,10 @@ def bench_prefill(args, model, idx, lens):
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) * 1e3, out
 
-    times = {"native": [], "sdpa": []}
+    other = ("paged", paged) if args.paged else ("sdpa", sdpa)
+    times = {"native": [], other[0]: []}
     for r in range(3 + args.runs):
-        for name, f in (("native", native), ("sdpa", sdpa)):
+        for name, f in (("native", native), other):
             ms, out = timed(f)
             if r >= 3:
                 times[name].append(ms)
@@ -154,6 +364,13 @@ def bench_prefill(args, model, idx, lens):
                 first = out if name == "native" else first
                 diff = float((out.float() - first.float()).abs().max())
     med = {k: statistics.median(v) for k, v in times.items()}
+    if args.paged:
+        print(f"{args.model_size} {args.dtype} prefill batch {B} lens {min(lens)}..{max(lens)}"
+              f" chunk {args.prefill_chunk}: contiguous {med['native']:.2f} ms "
+              f"(min {min(times['native']):.2f}), paged {med['paged']:.2f} ms "
+              f"(min {min(times['paged']):.2f}), ratio {med['paged'] / med['native']:.3f}x; "
+              f"max |logit diff| {diff:.3f}")
+        return
     print(f"{args.model_size} {args.dtype} prefill batch {B} lens {min(lens)}..{max(lens)}"
           f" chunk {args.prefill_chunk}: native {med['native']:.2f} ms "
           f"(min {min(times['native']):.2f}), sdpa forward {med['sdpa']:.2f} ms "

@@ -55,6 +55,16 @@ class StaticKVCache:
         the active ones grow). Device adds: correct inside a graph replay."""
         self.len_t += n
 
+    # The attention layers reach a cache through these two calls, so that
+    # another cache kind (models/paged.py) brings its own addressing.
+    def attend_decode(self, layer_idx, qkv, num_head, slopes):
+        return ops.attention_decode_append(
+            qkv, self.k[layer_idx], self.v[layer_idx], num_head, slopes, self.len_t)
+
+    def attend_prefill(self, layer_idx, qkv, num_head, slopes, lens, start):
+        return ops.attention_prefill_append(
+            qkv, self.k[layer_idx], self.v[layer_idx], num_head, slopes, lens, start)
+
     def set_len(self, n):
         """An int (every sequence) or a length-B sequence / tensor."""
         if isinstance(n, int):
@@ -125,9 +135,7 @@ class InferenceAttention(nn.Module):
                 # row, appends k / v at device position len-1 (len already
                 # advanced for this token, per sequence) and attends over
                 # the live cache — fully graph-replayable
-                out = ops.attention_decode_append(
-                    qkv, static_cache.k[layer_idx], static_cache.v[layer_idx],
-                    H, self.slopes, static_cache.len_t)
+                out = static_cache.attend_decode(layer_idx, qkv, H, self.slopes)
                 return _proj(out, self.fc_resid.weight), None
             q, k, v = qkv.split(C, dim=-1)
             q = q.view(B, T, H, D).transpose(1, 2)
@@ -138,6 +146,8 @@ class InferenceAttention(nn.Module):
             k = _proj(x, self.key.weight).view(B, T, H, D).transpose(1, 2)
             v = _proj(x, self.value.weight).view(B, T, H, D).transpose(1, 2)
         if static_cache is not None:
+            assert isinstance(static_cache, StaticKVCache), \
+                "a paged cache is filled through GPT2.prefill"
             kc, vc = static_cache.k[layer_idx], static_cache.v[layer_idx]
             # prefill: fill rows [0, T) and fall through to the SDPA path
             idxs = torch.arange(T, device=x.device)
@@ -182,9 +192,8 @@ class InferenceAttention(nn.Module):
         rows start[b]..start[b]+lens[b] and attends over the cache; no mask
         tensor, no index_copy_), the output projection."""
         qkv = F.linear(x, self._fused_qkv_w(x.dtype))
-        out = ops.attention_prefill_append(
-            qkv, cache.k[layer_idx], cache.v[layer_idx], self.num_head,
-            self.slopes, lens, start)
+        out = cache.attend_prefill(layer_idx, qkv, self.num_head, self.slopes,
+                                   lens, start)
         return F.linear(out, self.fc_resid.weight)
 
 
@@ -304,9 +313,15 @@ class GPT2(nn.Module):
         cache: StaticKVCache,
         lens=None,
         chunk: Optional[int] = None,
+        start=None,
     ) -> torch.Tensor:
         """Fill `cache` from the prompts and return each sequence's
         last-token logits, (B, V).
+
+        `cache` is a StaticKVCache, or a paged cache or a view of some of its
+        slots (models/paged.py). `start` (None: nothing) is the number of rows
+        each sequence already has cached, e.g. a shared prefix: idx then holds
+        the tokens behind them, and `lens` counts those.
 
         idx: (B, T) right-padded prompts; lens: one length per sequence (a
         sequence or a (B,) tensor; None: all T). Per layer: one fused qkv
@@ -330,6 +345,8 @@ class GPT2(nn.Module):
             lens_t = torch.full((B,), T, dtype=torch.int32, device=dev)
         else:
             lens_t = torch.as_tensor(lens, dtype=torch.int32).to(dev)
+        start_t = (None if start is None
+                   else torch.as_tensor(start, dtype=torch.int32).to(dev))
         P = T if not chunk else max(1, min(int(chunk), T))
         rows = torch.arange(B, device=dev)
         last = None
@@ -338,6 +355,8 @@ class GPT2(nn.Module):
             Pc = x.shape[1]
             lens_c = (lens_t - c0).clamp(0, Pc)
             start_c = lens_t.clamp(max=c0)
+            if start_t is not None:
+                start_c = start_c + start_t
             for i, block in enumerate(self.blocks):
                 x = x + block.attn.prefill(block.ln1(x), cache, i, lens_c, start_c)
                 x = x + block.mlp(block.ln2(x))

@@ -411,6 +411,70 @@ def attention_prefill_append(
         qkv.contiguous(), k_cache, v_cache, slopes, lens, start)
 
 
+def _paged_on_gpu(qkv: torch.Tensor, k_pool: torch.Tensor, dims) -> bool:
+    # rows per page that are no multiple of 64 are an error there, not a
+    # reason to leave the GPU: the kernels' check raises
+    return (
+        qkv.is_cuda
+        and qkv.dtype in (torch.float16, torch.bfloat16)
+        and dims(k_pool.shape[3])
+    )
+
+
+def attention_prefill_paged(
+    qkv: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor,
+    num_head: int, slopes: Optional[torch.Tensor], block_table: torch.Tensor,
+    lens: Optional[torch.Tensor] = None,
+    start: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """attention_prefill_append on a paged KV cache: qkv (B,T,3C), k_pool /
+    v_pool (P,H,R,D) of qkv's dtype, written in place -> (B,T,C).
+
+    `block_table`: (B, M) int32 on qkv's device. Logical cache row j of
+    sequence b is pool[block_table[b, j // R], :, j % R]; S_alloc = M*R and
+    `lens` / `start` mean what they mean for attention_prefill_append. Page
+    ids are clamped to [0, P); table entries past the last live page are
+    never used as a page id. On GPU (fp16/bf16, head_dim 32/64/96/128; R % 64 != 0 raises)
+    the kernels of ops/csrc/attn_paged.hip read and write the pool through
+    the table; everything else takes the fp32 reference (gather, contiguous
+    reference, scatter). Inference only (no autograd)."""
+    if not _paged_on_gpu(qkv, k_pool, lambda d: d in (32, 64, 96, 128)):
+        return reference.attention_prefill_paged(
+            qkv, k_pool, v_pool, num_head, slopes, block_table, lens, start)
+    assert k_pool.shape[1] == num_head, "k_pool heads != num_head"
+    B, T = qkv.shape[:2]
+    if slopes is None:
+        slopes = torch.zeros(num_head, dtype=torch.float32, device=qkv.device)
+    if lens is None:
+        lens = torch.full((B,), T, dtype=torch.int32, device=qkv.device)
+    if start is None:
+        start = torch.zeros(B, dtype=torch.int32, device=qkv.device)
+    return hip_ops().attn_prefill_paged(
+        qkv.contiguous(), k_pool, v_pool, slopes, block_table, lens, start)
+
+
+def attention_decode_paged(
+    qkv: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor,
+    num_head: int, slopes: Optional[torch.Tensor], block_table: torch.Tensor,
+    lens: torch.Tensor,
+) -> torch.Tensor:
+    """attention_decode_append on a paged KV cache (layout as in
+    attention_prefill_paged): qkv (B,1,3C) -> (B,1,C); the new k/v row goes
+    to logical row lens[b]-1 of sequence b, through the table. `lens` and
+    `block_table` are read in-kernel, so a captured graph serves a changing
+    set of sequences; lens[b] == 0 is an empty slot (nothing written, zeros
+    returned). GPU: fp16/bf16, head_dim <= 256 (R % 64 != 0 raises); everything
+    else takes the fp32 reference. Inference only (no autograd)."""
+    if not _paged_on_gpu(qkv, k_pool, lambda d: d <= 256):
+        return reference.attention_decode_paged(
+            qkv, k_pool, v_pool, num_head, slopes, block_table, lens)
+    assert k_pool.shape[1] == num_head, "k_pool heads != num_head"
+    if slopes is None:
+        slopes = torch.zeros(num_head, dtype=torch.float32, device=qkv.device)
+    return hip_ops().attn_decode_paged(
+        qkv.contiguous(), k_pool, v_pool, slopes, block_table, lens)
+
+
 # ---------------------------------------------------------------------------
 # Fused residual-add + dropout:  y = x + dropout(h, p)
 # ---------------------------------------------------------------------------

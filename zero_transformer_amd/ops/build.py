@@ -30,6 +30,7 @@ SOURCES = [
     "attention_fwd.hip",
     "attn_decode.hip",
     "attn_prefill.hip",
+    "attn_paged.hip",
     "attention_bwd.hip",
     "gemm_lt.hip",
     "gemv.hip",

@@ -28,6 +28,12 @@ at::Tensor attn_decode_append(at::Tensor qkv, at::Tensor k_cache,
 at::Tensor attn_prefill_append(at::Tensor qkv, at::Tensor k_cache,
                                at::Tensor v_cache, at::Tensor slopes,
                                at::Tensor lens, at::Tensor start);
+at::Tensor attn_prefill_paged(at::Tensor qkv, at::Tensor k_pool, at::Tensor v_pool,
+                              at::Tensor slopes, at::Tensor block_table,
+                              at::Tensor lens, at::Tensor start);
+at::Tensor attn_decode_paged(at::Tensor qkv, at::Tensor k_pool, at::Tensor v_pool,
+                             at::Tensor slopes, at::Tensor block_table,
+                             at::Tensor lens);
 std::vector<at::Tensor> attn_fwd(at::Tensor qkv, at::Tensor slopes, int64_t H,
                                  double p_drop, int64_t seed);
 std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor qkv, at::Tensor slopes,
@@ -56,6 +62,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "prefill attention on the fused qkv rows against the KV cache, with "
         "per-sequence new-row counts and cached-row offsets; fills the caches "
         "in place (gfx950 MFMA)");
+  m.def("attn_prefill_paged", &attn_prefill_paged,
+        "attn_prefill_append on a paged KV pool (P, H, R, D) addressed through a "
+        "(B, M) block table (gfx950 MFMA)");
+  m.def("attn_decode_paged", &attn_decode_paged,
+        "attn_decode_append on a paged KV pool (P, H, R, D) addressed through a "
+        "(B, M) block table (gfx950)");
   m.def("attn_fwd", &attn_fwd, "fused causal ALiBi flash attention fwd (gfx950 MFMA)");
   // fused: -1 = process default (ZTA_BWD_FUSED), 0 = two-kernel dq + dkdv,
   // 1 = single fused kernel (head_dim 128; other dims take the two-kernel path)

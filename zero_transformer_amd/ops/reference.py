@@ -170,6 +170,78 @@ def attention_prefill_append(
     return out.to(qkv.dtype)
 
 
+def paged_gather(pool: torch.Tensor, block_table: torch.Tensor) -> torch.Tensor:
+    """The logical caches of a paged pool: pool (P, H, R, D), block_table
+    (B, M) -> (B, H, M*R, D), a copy. Page ids are clamped to [0, P)."""
+    P, H, R, D = pool.shape
+    B, M = block_table.shape
+    pages = pool[block_table.long().clamp(0, P - 1)]  # (B, M, H, R, D)
+    return pages.permute(0, 2, 1, 3, 4).reshape(B, H, M * R, D)
+
+
+def _paged_scatter_rows(pool, block_table, cache, b: int, lo: int, hi: int) -> None:
+    """pool rows of sequence b's logical rows [lo, hi) <- cache[b, :, lo:hi]."""
+    P, _, R, _ = pool.shape
+    for j in range(lo, hi):
+        page = min(max(int(block_table[b, j // R]), 0), P - 1)
+        pool[page, :, j % R] = cache[b, :, j]
+
+
+def attention_prefill_paged(
+    qkv: torch.Tensor,
+    k_pool: torch.Tensor,
+    v_pool: torch.Tensor,
+    num_head: int,
+    slopes: Optional[torch.Tensor],
+    block_table: torch.Tensor,
+    lens: Optional[torch.Tensor] = None,
+    start: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """attention_prefill_append on a paged cache: k_pool / v_pool (P, H, R, D)
+    written in place, block_table (B, M) int32; logical row j of sequence b is
+    pool[block_table[b, j // R], :, j % R] and S_alloc = M * R. Gathers each
+    sequence's pages, runs the contiguous reference and scatters the rows it
+    wrote, [st, st + n), back: no other pool row changes."""
+    B, T, _ = qkv.shape
+    R = k_pool.shape[2]
+    S_alloc = block_table.shape[1] * R
+    k = paged_gather(k_pool, block_table)
+    v = paged_gather(v_pool, block_table)
+    out = attention_prefill_append(qkv, k, v, num_head, slopes, lens, start)
+    lens_l = [T] * B if lens is None else lens.tolist()
+    start_l = [0] * B if start is None else start.tolist()
+    for b in range(B):
+        st = min(max(int(start_l[b]), 0), S_alloc)
+        n = min(max(int(lens_l[b]), 0), min(T, S_alloc - st))
+        _paged_scatter_rows(k_pool, block_table, k, b, st, st + n)
+        _paged_scatter_rows(v_pool, block_table, v, b, st, st + n)
+    return out
+
+
+def attention_decode_paged(
+    qkv: torch.Tensor,
+    k_pool: torch.Tensor,
+    v_pool: torch.Tensor,
+    num_head: int,
+    slopes: Optional[torch.Tensor],
+    block_table: torch.Tensor,
+    lens: torch.Tensor,
+) -> torch.Tensor:
+    """attention_decode_append on a paged cache (layout as in
+    attention_prefill_paged): the new row lands at logical row lens[b] - 1 of
+    sequence b; lens[b] == 0 writes nothing and returns zeros."""
+    S_alloc = block_table.shape[1] * k_pool.shape[2]
+    k = paged_gather(k_pool, block_table)
+    v = paged_gather(v_pool, block_table)
+    out = attention_decode_append(qkv, k, v, num_head, slopes, lens)
+    for b, S in enumerate(lens.tolist()):
+        S = min(max(int(S), 0), S_alloc)
+        if S:
+            _paged_scatter_rows(k_pool, block_table, k, b, S - 1, S)
+            _paged_scatter_rows(v_pool, block_table, v, b, S - 1, S)
+    return out
+
+
 def drop_mask(seed: int, B: int, H: int, T: int, p: float) -> torch.Tensor:
     """Regenerate the attention-dropout keep mask of the HIP kernels.
 
