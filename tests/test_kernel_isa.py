@@ -87,3 +87,27 @@ a.hip:9:1: remark:     LDS Size [bytes/block]: 0 [-Rpass-analysis=kernel-resourc
     assert K.resources(rem) == {"_Z3foov": {
         "vgpr": "230", "agpr": "160", "scratch": "316", "occ": "1",
         "sspill": "16", "vspill": "98", "lds": "0"}}
+
+
+def test_rename_pairs_by_demangled_name():
+    names = {"_Z3foov": "foo<1>", "_Z3barv": "bar", "_Z3quxv": "qux<1, false>",
+             "_Z3zapv": "zap<1, false>"}
+    ren = [K.rename_arg(r"foo<(.*)>=qux<\1, false>")]
+    base = K.kernels(A)
+
+    def run(new_foo_sym, add):
+        new = K.kernels(_func(0, new_foo_sym, _body(0, add))
+                        + _func(1, "_Z3barv", _body(1, "v_mul_f32_e32 v0, v0, v1")))
+        to = K.renamed(base, new, names, ren)
+        return to, K.compare({to.get(s, s): t for s, t in base.items()}, new)
+
+    # foo<1> -> qux<1, false>, equal text / one instruction changed
+    to, res = run("_Z3quxv", "v_add_f32_e32 v0, v0, v1")
+    assert to == {"_Z3foov": "_Z3quxv"}
+    assert res == {"_Z3barv": "same", "_Z3quxv": "same"}
+    _, res = run("_Z3quxv", "v_sub_f32_e32 v0, v0, v1")
+    assert res == {"_Z3barv": "same", "_Z3quxv": "DIFF"}
+    # no kernel carries the renamed name: nothing is paired
+    to, res = run("_Z3zapv", "v_add_f32_e32 v0, v0, v1")
+    assert to == {}
+    assert res == {"_Z3barv": "same", "_Z3foov": "removed", "_Z3zapv": "added"}

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compare the gfx950 code of every kernel in a .hip file with a git revision.
 
-    tools/kernel_isa.py FILE.hip [--base REV]
+    tools/kernel_isa.py FILE.hip [--base REV] [--rename OLD=NEW]...
 
 Compiles the working-tree FILE and the copy of it in REV (default HEAD; the
 whole ops/csrc directory is extracted, so headers come along) to device
@@ -9,6 +9,11 @@ assembly with the flags of ops/build.py and prints, per kernel, same / DIFF /
 added / removed plus both versions' register, spill, scratch, occupancy and
 LDS figures. Exits non-zero if a kernel present on both sides differs. Run it
 after every kernel edit: a refactor must leave every kernel `same`.
+
+Kernels are paired by symbol. --rename pairs a kernel of REV with the
+working-tree kernel whose demangled name is REV's with the regular expression
+OLD replaced by NEW, e.g. for a renamed template with one more argument
+    --rename 'old_kernel<(.*)>=new_kernel<\1, false>'
 """
 
 from __future__ import annotations
@@ -63,6 +68,29 @@ def compare(base: dict, new: dict) -> dict:
     return res
 
 
+def renamed(base, new, names: dict, renames: list) -> dict:
+    """base symbol -> the symbol in `new` that carries its name after the
+    (old regex, replacement) pairs in `renames`, for every base symbol whose
+    name they change and that has such a counterpart. names: symbol ->
+    demangled name."""
+    by_name = {names[s]: s for s in new}
+    out = {}
+    for sym in base:
+        name = names[sym]
+        for old, repl in renames:
+            name = re.sub(old, repl, name)
+        if name != names[sym] and name in by_name:
+            if by_name[name] in base:
+                sys.exit(f"--rename maps {names[sym]} onto {name}, which the base has too")
+            out[sym] = by_name[name]
+    return out
+
+
+def rename_arg(s: str) -> tuple:
+    old, new = s.split("=", 1)  # ValueError without "=": argparse reports it
+    return old, new
+
+
 def resources(remarks: str) -> dict:
     """symbol -> {column: value} from -Rpass-analysis=kernel-resource-usage."""
     out, cur = {}, None
@@ -100,6 +128,8 @@ def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("file")
     ap.add_argument("--base", default="HEAD")
+    ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW",
+                    type=rename_arg)
     a = ap.parse_args()
     sys.path.insert(0, ROOT)
     rel = os.path.relpath(os.path.abspath(a.file), ROOT)
@@ -112,14 +142,17 @@ def main() -> int:
             fb = ex.submit(compile_asm, old) if os.path.exists(old) else None
             new, new_res = ex.submit(compile_asm, os.path.join(ROOT, rel)).result()
             base, base_res = fb.result() if fb else ({}, {})
+    names = demangle(sorted(set(base) | set(new)))
+    to = renamed(base, new, names, a.rename)
+    was = {n: f" (was {names[b]})" for b, n in to.items()}
+    base, base_res = ({to.get(s, s): v for s, v in d.items()} for d in (base, base_res))
     status = compare(base, new)
-    names = demangle(list(status))
     print(f"{rel}: working tree vs {a.base}   (" + " ".join(c for _, c in FIELDS) + "; base -> new)")
     for sym, st in status.items():
         cols = ["/".join(r.get(sym, {}).get(c, "-") for _, c in FIELDS)
                 + f" {k[sym].count(chr(10)) + 1 if sym in k else '-'} lines"
                 for r, k in ((base_res, base), (new_res, new))]
-        print(f"{st:8s}{names[sym]}:  {cols[0]} -> {cols[1]}")
+        print(f"{st:8s}{names[sym]}{was.get(sym, '')}:  {cols[0]} -> {cols[1]}")
     return int("DIFF" in status.values())
 
 

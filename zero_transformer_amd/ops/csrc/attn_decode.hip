@@ -53,7 +53,7 @@
 // blocks is needed; the next launch on the stream sees the row. S == 0 has no
 // key S - 1 and writes nothing.
 
-#include "common.h"
+#include "attn_kv.h"  // NEG_INF, attn_decode_merge_kernel
 
 #include <ATen/ATen.h>
 #include <ATen/hip/HIPContext.h>
@@ -63,7 +63,6 @@
 namespace {
 
 constexpr int NW = 4;  // waves per block
-constexpr float NEG_INF = -3.0e38f;
 
 template <int DPL, bool F16>
 __global__ __launch_bounds__(NW * 64) void attn_decode_split_kernel(
@@ -173,43 +172,6 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_split_kernel(
     }
 #pragma unroll
     for (int e = 0; e < DPL; ++e) pr[2 + lane + e * 64] = og[e];
-  }
-}
-
-template <int DPL, bool F16>
-__global__ __launch_bounds__(64) void attn_decode_merge_kernel(
-    const float* __restrict__ part, uint16_t* __restrict__ out, int D,
-    int splits) {
-  const int bh = blockIdx.x;
-  const int lane = threadIdx.x;
-  const float* base = &part[(long)bh * splits * (2 + 64 * DPL)];
-  float mg = NEG_INF;
-  for (int s = 0; s < splits; ++s)
-    mg = fmaxf(mg, base[s * (2 + 64 * DPL)]);
-  float lg = 0.f;
-  float og[DPL];
-#pragma unroll
-  for (int e = 0; e < DPL; ++e) og[e] = 0.f;
-  for (int s = 0; s < splits; ++s) {
-    const float* pr = &base[s * (2 + 64 * DPL)];
-    const float f = pr[0] > 0.5f * NEG_INF ? __expf(pr[0] - mg) : 0.f;
-    lg += pr[1] * f;
-#pragma unroll
-    for (int e = 0; e < DPL; ++e) og[e] += pr[2 + lane + e * 64] * f;
-  }
-  const float inv = lg > 0.f ? 1.f / lg : 0.f;
-#pragma unroll
-  for (int e = 0; e < DPL; ++e) {
-    const int d = lane + e * 64;
-    if (d < D) {
-      const float o = og[e] * inv;
-      if (F16) {
-        __half hv = __float2half(o);
-        out[(long)bh * D + d] = *reinterpret_cast<uint16_t*>(&hv);
-      } else {
-        out[(long)bh * D + d] = f32_to_bf16(o);
-      }
-    }
   }
 }
 

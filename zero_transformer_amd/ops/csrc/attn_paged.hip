@@ -42,21 +42,38 @@
 // memory. Partition (chunk = ceil(S / 8)), per-wave order and merge are those
 // of attn_decode.hip, so the result does not depend on R or on the table.
 //
-// The device helpers, the flash kernel body and the merge kernel are copies of
-// the ones in attn_prefill.hip / attn_decode.hip, which stay untouched: their
-// kernels' code is pinned by tools/kernel_isa.py. Sharing the flash body was
-// tried, as a header template over a "stager" (first tile / next tile) that
-// both kernels wrapped: it does not leave the contiguous kernel as it is. All
-// eight prefill_flash_kernel instantiations came out different (D 128: 2215 ->
-// 2245 instructions at 210 VGPRs; D 32: 123 -> 111 VGPRs, 1805 -> 1728; D 96:
-// 188 -> 176 VGPRs), and so did the paged ones, so it would need its own
-// timing run of the prompt pass. A change to the scheme has to be made in
-// both files until then; the two bodies differ only in the staging calls
-// (`stage`, `pg_next` here; the two glds_stage pairs there).
+// The helpers and the merge kernel are those of attn_kv.h. paged_flash_kernel
+// is a second copy of prefill_flash_kernel's body (attn_kv.h), differing only
+// in the staging calls (`stage`, `pg_next` here; the two glds_stage pairs
+// there): a change to the scheme has to be made in both. One source body was
+// tried in three forms (tools/kernel_isa.py against both kernels). The tile
+// body and epilogue as ZTA_DEV functions, or the whole body as a ZTA_DEV
+// template under two thin kernels, change the contiguous kernel (D 32: 123 ->
+// 112 / 111 VGPRs; D 128: 210 -> 212; D 96: 188 -> 176). One __global__
+// template with `if constexpr (PAGED)` at the staging sites and the paged
+// arguments (bt, pl) last leaves all eight contiguous instantiations the same
+// and the paged ones the same but for the argument order (+1..2 instructions,
+// same registers), yet the paged prompt pass measured slower with it than
+// with this copy, 1.3B fp16, paged column of tools/decode_bench.py --prefill
+// --paged, copy / template / copy / template in one session, ms:
+//   batch 1, prompt 128    3.48 / 3.23 / 3.40 / 3.41
+//   batch 1, prompt 1024   5.55 / 5.79 / 5.62 / 5.77   (again 5.59 / 5.72 /
+//                          5.49 / 5.61 / 5.50 / 5.73)
+//   batch 1, prompt 2048   8.86 / 9.34 / 8.86 / 8.89   (again 8.94 / 8.92 /
+//                          8.88 / 8.97 / 8.91 / 8.86)
+//   batch 16, uniform 128  6.92 / 6.78 / 6.58 / 6.70
+//   batch 16, 54..119      6.44 / 6.45 / 6.45 / 6.44
+// The 1024 row is beyond the copy's own spread both times, so the copy stays.
+// Kernel traces put 0.8 us per call (54.2 -> 55.0 us) of that in the kernel;
+// the rest is not explained (profiles/PERF.md "Shared KV flash kernel").
+// The decode split kernels here and in attn_decode.hip are separate on
+// purpose: moving only the block-merge tail into a ZTA_DEV function, or
+// running the contiguous case as one segment of the paged segment loop,
+// changed all eight contiguous instantiations (36-97 lines each) of the
+// latency-bound kernel of batch-1 decode.
 // No atomics: both ops are deterministic.
 
-#include "attn_tiles.h"
-#include "common.h"
+#include "attn_kv.h"
 
 #include <ATen/ATen.h>
 #include <ATen/hip/HIPContext.h>
@@ -66,80 +83,6 @@
 #include <type_traits>
 
 namespace {
-
-using attn::TB;
-using attn::swz;
-
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
-
-constexpr float NEG_INF = -3.0e38f;
-
-// Two f32 -> one packed word of the element type, round to nearest even.
-template <bool F16>
-ZTA_DEV unsigned pack2(float a, float b) {
-  if constexpr (F16) {
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a, b}, f16x2));
-  } else {
-    unsigned w;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(w) : "v"(a), "v"(b));
-    return w;
-  }
-}
-
-template <bool F16>
-ZTA_DEV f32x16 mfma16(bf16x8 a, bf16x8 b, f32x16 c) {
-  if constexpr (F16) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a),
-                                                  __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  } else {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-  }
-}
-
-// attn::c_to_a_frags for either element type (same register shuffle).
-template <bool F16>
-ZTA_DEV void p_to_a_frags(const float* x, bf16x8* pa) {
-  unsigned w[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) w[j] = pack2<F16>(x[2 * j], x[2 * j + 1]);
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    auto r0 = __builtin_amdgcn_permlane32_swap(w[4 * j + 0], w[4 * j + 2], false, false);
-    w[4 * j + 0] = r0[0];
-    w[4 * j + 2] = r0[1];
-    auto r1 = __builtin_amdgcn_permlane32_swap(w[4 * j + 1], w[4 * j + 3], false, false);
-    w[4 * j + 1] = r1[0];
-    w[4 * j + 3] = r1[1];
-  }
-  union {
-    unsigned u[4];
-    bf16x8 v8;
-  } cvt;
-  cvt.u[0] = w[0]; cvt.u[1] = w[1]; cvt.u[2] = w[2]; cvt.u[3] = w[3];
-  pa[0] = cvt.v8;
-  cvt.u[0] = w[4]; cvt.u[1] = w[5]; cvt.u[2] = w[6]; cvt.u[3] = w[7];
-  pa[1] = cvt.v8;
-}
-
-// Pool geometry: P pages of R rows; a sequence's table row has M entries.
-struct Pool {
-  int P, R, M;
-};
-
-struct SeqRange {
-  int st, n;
-};
-ZTA_DEV SeqRange seq_range(const int* lens, const int* start, int b, int T, int cap) {
-  const int st = min(max(start[b], 0), cap);
-  const int n = min(max(lens[b], 0), min(T, cap - st));
-  return {st, n};
-}
-
-// Page of logical page index pi (< M) of sequence b, clamped to the pool.
-ZTA_DEV int page_of(const int* __restrict__ bt, int b, int pi, Pool pl) {
-  return min(max(bt[(long)b * pl.M + pi], 0), pl.P - 1);
-}
 
 // One item = 8 elements (16 B) of the K or V columns of one qkv row.
 __global__ __launch_bounds__(256) void paged_append_kernel(
@@ -373,9 +316,6 @@ __global__ __launch_bounds__(NT, 2) void paged_flash_kernel(
   }
 }
 
-// 128 q rows per block, as attn_prefill.hip's PREFILL_NT (measured there).
-constexpr int PAGED_NT = 256;
-
 // ---------------------------------------------------------------------------
 // Decode
 // ---------------------------------------------------------------------------
@@ -507,42 +447,6 @@ __global__ __launch_bounds__(NW * 64) void paged_decode_split_kernel(
   }
 }
 
-// attn_decode_merge_kernel of attn_decode.hip.
-template <int DPL, bool F16>
-__global__ __launch_bounds__(64) void paged_decode_merge_kernel(
-    const float* __restrict__ part, uint16_t* __restrict__ out, int D, int splits) {
-  const int bh = blockIdx.x;
-  const int lane = threadIdx.x;
-  const float* base = &part[(long)bh * splits * (2 + 64 * DPL)];
-  float mg = NEG_INF;
-  for (int s = 0; s < splits; ++s) mg = fmaxf(mg, base[s * (2 + 64 * DPL)]);
-  float lg = 0.f;
-  float og[DPL];
-#pragma unroll
-  for (int e = 0; e < DPL; ++e) og[e] = 0.f;
-  for (int s = 0; s < splits; ++s) {
-    const float* pr = &base[s * (2 + 64 * DPL)];
-    const float f = pr[0] > 0.5f * NEG_INF ? __expf(pr[0] - mg) : 0.f;
-    lg += pr[1] * f;
-#pragma unroll
-    for (int e = 0; e < DPL; ++e) og[e] += pr[2 + lane + e * 64] * f;
-  }
-  const float inv = lg > 0.f ? 1.f / lg : 0.f;
-#pragma unroll
-  for (int e = 0; e < DPL; ++e) {
-    const int d = lane + e * 64;
-    if (d < D) {
-      const float o = og[e] * inv;
-      if (F16) {
-        __half hv = __float2half(o);
-        out[(long)bh * D + d] = *reinterpret_cast<uint16_t*>(&hv);
-      } else {
-        out[(long)bh * D + d] = f32_to_bf16(o);
-      }
-    }
-  }
-}
-
 // Shared argument checks; returns the pool geometry.
 Pool check_paged(const char* op, const at::Tensor& qkv, const at::Tensor& kp,
                  const at::Tensor& vp, const at::Tensor& slopes, const at::Tensor& bt,
@@ -599,11 +503,11 @@ at::Tensor attn_prefill_paged(at::Tensor qkv, at::Tensor k_pool, at::Tensor v_po
                        (uint16_t*)k_pool.data_ptr(), (uint16_t*)v_pool.data_ptr(), tp, lp,
                        sp, B, H, T, C, D, pl);
     const size_t smem = 4 * TB * 128 * sizeof(uint16_t);  // 2 tensors x 2 buffers
-    constexpr int QROWS = PAGED_NT / 2;
+    constexpr int QROWS = PREFILL_NT / 2;
     dim3 grid(B * H, (T + QROWS - 1) / QROWS);
     auto launch = [&](auto f16c) {
-      hipLaunchKernelGGL((paged_flash_kernel<DD, PAGED_NT, decltype(f16c)::value>), grid,
-                         dim3(PAGED_NT), smem, stream, (const uint16_t*)qkv.data_ptr(),
+      hipLaunchKernelGGL((paged_flash_kernel<DD, PREFILL_NT, decltype(f16c)::value>), grid,
+                         dim3(PREFILL_NT), smem, stream, (const uint16_t*)qkv.data_ptr(),
                          (const uint16_t*)k_pool.data_ptr(),
                          (const uint16_t*)v_pool.data_ptr(), sl.data_ptr<float>(),
                          (uint16_t*)o.data_ptr(), tp, lp, sp, H, T, C, pl,
@@ -646,7 +550,7 @@ at::Tensor attn_decode_paged(at::Tensor qkv, at::Tensor k_pool, at::Tensor v_poo
                        part.data_ptr<float>(), block_table.data_ptr<int>(),
                        lens.data_ptr<int>(), H, (int)C, D, pl, r_shift,
                        1.0f / sqrtf((float)D), splits);
-    hipLaunchKernelGGL((paged_decode_merge_kernel<DPL, F>), dim3(B * H), dim3(64), 0,
+    hipLaunchKernelGGL((attn_decode_merge_kernel<DPL, F>), dim3(B * H), dim3(64), 0,
                        stream, part.data_ptr<float>(), (uint16_t*)out.data_ptr(), D, splits);
   };
   auto by_type = [&](auto dplc) {
