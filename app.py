@@ -13,12 +13,15 @@ Two modes:
   Several --prompt flags on the CLI go through the same batched path and
   print one completion per line.
   Paged:  python app.py ... --serve --paged --slots 16 --kv-pages 512
-          POST /submit {"prompt": ..., "max_new_tokens": ...} -> {"completion": ...}
+          POST /submit {"prompt": ..., "max_new_tokens": ..., ...same options...,
+                        "seed": S (optional)} -> {"completion": ...}
           One engine thread (models/paged.py ServingEngine: paged KV cache,
           continuous batching, prefix reuse) serves every /submit: a request
           joins the running batch and its call returns when it is done. The
-          sampling options are the server's (the command line's), not the
-          request's.
+          sampling options are the request's, with the defaults of /generate;
+          a body that names none of them takes the server's (the command
+          line's). The same prompt, options and "seed" give the same
+          completion, whatever else is in the batch.
 
 Tokenizer: GPT-NeoX-20B via transformers when its assets are cached locally
 (reference app.py:27); otherwise a byte-level fallback so the app works on
@@ -100,11 +103,12 @@ class EngineWorker:
         self.thread = threading.Thread(target=self._loop, daemon=True)
         self.thread.start()
 
-    def submit(self, tokens, max_new_tokens: int) -> list:
+    def submit(self, tokens, max_new_tokens: int, **options) -> list:
+        """`options`: ServingEngine.submit's sampling options and seed."""
         import threading
 
         done, box = threading.Event(), {}
-        self.inbox.put((tokens, max_new_tokens, done, box))
+        self.inbox.put((tokens, max_new_tokens, done, box, options))
         # a timed wait: a request queued after the thread has died is caught
         # here, not by the thread's own clean-up
         while not done.wait(0.5):
@@ -115,10 +119,10 @@ class EngineWorker:
         return box["tokens"]
 
     def _take(self, item) -> None:
-        tokens, n, done, box = item
+        tokens, n, done, box, options = item
         try:
-            self.pending[self.engine.submit(tokens, n)] = (done, box)
-        except ValueError as e:  # a request that can never fit
+            self.pending[self.engine.submit(tokens, n, **options)] = (done, box)
+        except ValueError as e:  # a request that can never fit, or a bad option
             box["error"] = e
             done.set()
 
@@ -140,7 +144,7 @@ class EngineWorker:
             while True:
                 item = self.inbox.get_nowait()
                 if item is not None:
-                    waiting.append(item[2:])
+                    waiting.append(item[2:4])
         except queue.Empty:
             pass
         for done, box in waiting:
@@ -188,6 +192,23 @@ def _options(req: dict) -> dict:
         prefill_chunk=(int(req["prefill_chunk"])
                        if req.get("prefill_chunk") is not None else None),
     )
+
+
+SAMPLING_FIELDS = ("temperature", "top_k", "top_p", "repetition_penalty", "greedy")
+
+
+def _submit_options(req: dict) -> dict:
+    """The options of a /submit body for ServingEngine.submit: those of
+    _options if the body names a sampling field, else none of them (the
+    engine's own defaults); "seed" whenever it is given."""
+    out = {}
+    if any(k in req for k in SAMPLING_FIELDS):
+        o = _options(req)
+        out = {k: o[k] for k in ("temperature", "top_k", "top_p",
+                                 "repetition_penalty", "sample")}
+    if req.get("seed") is not None:
+        out["seed"] = int(req["seed"])
+    return out
 
 
 def main():
@@ -274,7 +295,8 @@ def build_app(model, tok, device, engine=None):
             # a sync endpoint: each call waits in its own server thread
             try:
                 toks = worker.submit(tok.encode(str(req["prompt"])),
-                                     int(req.get("max_new_tokens", 128)))
+                                     int(req.get("max_new_tokens", 128)),
+                                     **_submit_options(req))
             except ValueError as e:
                 raise HTTPException(status_code=400, detail=str(e))
             except RuntimeError as e:

@@ -6,13 +6,18 @@
     python tools/decode_bench.py --model-size 1_3b --batch 16 --fast --paged
     python tools/decode_bench.py --model-size 1_3b --batch 16 --stream 64
     python tools/decode_bench.py --model-size 1_3b --batch 16 --stream 64 --prefix-len 512
+    python tools/decode_bench.py --model-size 1_3b --batch 16 --stream 64 --sample
+    python tools/decode_bench.py --sampler
 
 --paged runs the same workload through the paged KV cache (models/paged.py):
 --fast [--ragged] through a ServingEngine with --batch slots, --prefill through
 GPT2.prefill on a PagedKVCache. --stream N is the serving scenario: N seeded
 requests (prompts of 54..119 tokens, 16..256 new tokens each) through an
 engine with --batch slots, against generate_batch over the same requests in
-arrival-order groups of --batch.
+arrival-order groups of --batch; with --sample both sides sample at the
+server defaults (temperature 0.8, top-p 0.95, penalty 1.1), the engine with
+one seed per request. --sampler times the sampler alone, no model: the torch
+chain sampling.sample_batch against the fused ops.sample_rows kernel.
 """
 
 import argparse
@@ -64,11 +69,19 @@ def main():
     p.add_argument("--prefix-len", type=int, default=0,
                    help="with --stream: every prompt starts with the same "
                    "this-many tokens; the engine runs with and without prefix reuse")
+    p.add_argument("--sample", action="store_true",
+                   help="with --stream: sample at the server defaults instead of greedy")
+    p.add_argument("--sampler", action="store_true",
+                   help="time sample_batch against ops.sample_rows on fp16 "
+                   "(B, 50304) logits drawn from N(0, 3^2), B = 1 and 16, greedy "
+                   "and the server defaults; median of --runs rounds")
     p.add_argument("--kv-pages", type=int, default=0,
                    help="pages in the pool (0: what --batch full-length requests need)")
     p.add_argument("--prefill-chunk", type=int, default=None)
     p.add_argument("--runs", type=int, default=15)
     args = p.parse_args()
+    if args.sampler:
+        return bench_sampler(args)
     args.fast = args.fast or args.prefill or bool(args.stream) or args.step
     assert args.fast or not args.ragged, "--ragged goes with --fast"
     assert args.ragged or not args.sequential, "--sequential goes with --ragged"
@@ -174,6 +187,52 @@ def main():
           + (f"; engine reused {reuse[-1]:.1f} tokens/s" if args.paged else ""))
 
 
+SERVER_DEFAULTS = dict(temperature=0.8, top_k=0, top_p=0.95, repetition_penalty=1.1)
+
+
+@torch.no_grad()
+def bench_sampler(args):
+    """One sampling call of the serving step, the torch chain against the
+    fused kernel, on the same logits: fp16 (B, 50304) drawn from N(0, 3^2)
+    (no checkpoint), 5 % of each row marked seen. A timing is 200 calls
+    between two device syncs; 2 warm-up rounds, then --runs rounds that
+    alternate the two; median, min and max per call."""
+    from zero_transformer_amd import ops
+    from zero_transformer_amd.models.sampling import sample_batch
+
+    dev = torch.device("cuda", 0)
+    V, calls = 50304, 200
+    g = torch.Generator().manual_seed(0)
+    d = SERVER_DEFAULTS
+    for B in (1, 16):
+        logits = (torch.randn(B, V, generator=g) * 3).half().to(dev)
+        seen = (torch.rand(B, V, generator=g) < 0.05).to(dev)
+        vec = lambda v, dt: torch.full((B,), v, dtype=dt, device=dev)
+        seed = torch.arange(B, dtype=torch.long, device=dev)
+        counter = torch.zeros(B, dtype=torch.long, device=dev)
+        for name, sample in (("greedy", False), ("server defaults", True)):
+            rows = (logits, seen, vec(d["temperature"] if sample else 0.0, torch.float32),
+                    vec(d["top_k"], torch.int32), vec(d["top_p"], torch.float32),
+                    vec(d["repetition_penalty"], torch.float32), seed, counter)
+            fns = {"sample_batch": lambda: sample_batch(logits, seen, sample=sample, **d),
+                   "sample_rows": lambda: ops.sample_rows(*rows)}
+            times = {k: [] for k in fns}
+            for r in range(2 + args.runs):
+                for k, f in fns.items():
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for _ in range(calls):
+                        f()
+                    torch.cuda.synchronize()
+                    if r >= 2:
+                        times[k].append((time.perf_counter() - t0) / calls * 1e6)
+            med = {k: statistics.median(v) for k, v in times.items()}
+            print(f"sampler fp16 B {B} V {V} N(0, 3^2) {name}: "
+                  + ", ".join(f"{k} {med[k]:.1f} us (min {min(times[k]):.1f}, "
+                              f"max {max(times[k]):.1f})" for k in med)
+                  + f", sample_batch / sample_rows {med['sample_batch'] / med['sample_rows']:.2f}x")
+
+
 @torch.no_grad()
 def bench_step(args, model):
     """The captured decode step alone (no sampling, no prefill, no capture in
@@ -225,8 +284,10 @@ def bench_step(args, model):
 
 @torch.no_grad()
 def bench_stream(args, model):
-    """The serving scenario; greedy, no EOS, so both sides emit exactly the
-    requested tokens and only those are counted."""
+    """The serving scenario; no EOS, so both sides emit exactly the requested
+    tokens and only those are counted. Greedy, or with --sample at the server
+    defaults (the two sides then draw differently: token equality says
+    nothing)."""
     from zero_transformer_amd.models.inference import GRAPH_SCRATCH_ROWS, generate_batch
     from zero_transformer_amd.models.paged import ServingEngine
 
@@ -243,6 +304,7 @@ def bench_stream(args, model):
     row_bytes = 2 * model.N * attn.num_head * attn.head_dim * 2  # k + v, 16-bit
     full = -(-min(model.num_ctx, max(len(p) + m for p, m in zip(prompts, limits))) // 64)
     pages = args.kv_pages or S * full + 1
+    sampling = dict(SERVER_DEFAULTS, sample=True) if args.sample else {}
 
     class TimedEngine(ServingEngine):
         """Adds up the prefill time (a device sync on either side). A
@@ -270,7 +332,7 @@ def bench_stream(args, model):
         out, rows = [], 0
         for i in range(0, N, S):
             grp, lim = prompts[i:i + S], limits[i:i + S]
-            res = generate_batch(model, grp, max(lim))
+            res = generate_batch(model, grp, max(lim), **sampling)
             out += [r[:m] for r, m in zip(res, lim)]
             rows = max(rows, len(grp) * min(
                 model.num_ctx, max(len(p) + min(max(lim), model.num_ctx - len(p))
@@ -278,9 +340,10 @@ def bench_stream(args, model):
         return out, rows
 
     def engine(prefix_cache):
-        eng = TimedEngine(model, S, pages, prefix_cache=prefix_cache)
+        eng = TimedEngine(model, S, pages, prefix_cache=prefix_cache, **sampling)
         peak = 0
-        ids = [eng.submit(p, m) for p, m in zip(prompts, news)]
+        ids = [eng.submit(p, m, seed=i if args.sample else None)
+               for i, (p, m) in enumerate(zip(prompts, news))]
         res = {}
         while not eng.idle():
             eng.step()
@@ -294,7 +357,8 @@ def bench_stream(args, model):
     for _ in range(2):  # alternating, twice
         dt, (out_s, rows) = sync_time(static)
         assert sum(len(r) for r in out_s) == total
-        print(f"{args.model_size} {args.dtype} stream {N} x {S} static groups: "
+        print(f"{args.model_size} {args.dtype} stream {N} x {S} "
+              f"{'sampled' if args.sample else 'greedy'} static groups: "
               f"{total / dt:.1f} tokens/s ({dt:.2f} s), KV {rows * row_bytes / 2**20:.0f} MiB")
         for pc in ((True, False) if args.prefix_len else (True,)):
             dt, (out_e, eng, peak) = sync_time(lambda: engine(pc))

@@ -17,6 +17,7 @@ between requests through a hash chain of their token blocks.
 from __future__ import annotations
 
 import hashlib
+import math
 from collections import OrderedDict, deque
 from typing import Dict, List, Optional, Sequence
 
@@ -24,7 +25,6 @@ import torch
 
 from .. import ops
 from .inference import FINISHED_CHECK_EVERY, GPT2
-from .sampling import sample_batch
 
 
 class _PagedAttend:
@@ -184,11 +184,15 @@ class PagedKVCache(_PagedAttend):
 
 
 class _Request:
-    __slots__ = ("rid", "prompt", "limit", "slot", "shared", "keys")
+    __slots__ = ("rid", "prompt", "limit", "slot", "shared", "keys",
+                 "temperature", "top_k", "top_p", "penalty", "seed")
 
-    def __init__(self, rid, prompt, limit):
+    def __init__(self, rid, prompt, limit, temperature, top_k, top_p, penalty, seed):
         self.rid, self.prompt, self.limit = rid, prompt, limit
         self.slot, self.shared, self.keys = None, 0, None
+        # temperature 0 is greedy; seed None: the request draws nothing
+        self.temperature, self.top_k, self.top_p = temperature, top_k, top_p
+        self.penalty, self.seed = penalty, seed
 
 
 class ServingEngine:
@@ -206,7 +210,18 @@ class ServingEngine:
     steps until nothing is queued or running; poll() hands out what has
     finished since the last poll. A request yields at most
     min(max_new_tokens, num_ctx - len(prompt)) tokens, cut before `eos_token`
-    - generate_batch's rule. Sampling options are engine-wide.
+    - generate_batch's rule.
+
+    Sampling options are per request: submit() takes sample, temperature,
+    top_k, top_p, repetition_penalty and seed, and None means the
+    constructor's value. They live in per-slot device tensors written at
+    admission, and one ops.sample_rows call per step reads them per row.
+    Token i of a request is drawn with u = uniform01(seed, i), whoever shares
+    the batch, whichever slot it has and however many steps ran before: the
+    same prompt, options and seed give the same completion. A sampling
+    request without a seed gets one from torch's default CPU generator at
+    submit() (a greedy one draws nothing); info[rid]["seed"] holds the seed
+    in use. Tokens tied with the nucleus cut are all kept.
 
     Admission is all-or-nothing: a request enters only when every page it can
     ever need, ceil((len + limit) / page_rows) minus the shared ones, is free
@@ -218,7 +233,8 @@ class ServingEngine:
 
     The decode step is captured once, at construction, with every length 0
     and nothing active: such a step writes nothing. Population changes are
-    in-place device writes (block table, lengths, `cur`, `active`, `seen`)
+    in-place device writes (block table, lengths, `cur`, `active`, `seen`,
+    the sampling options)
     between replays. A slot with active = 0 (finished or empty) has length 0
     in the step, so it neither reads nor writes the pool. The host asks the
     device which rows have finished once per `check_every` steps, and when a
@@ -254,6 +270,7 @@ class ServingEngine:
                                   dev, p.dtype)
         self.eos_token = eos_token
         self.sampling = (temperature, top_k, top_p, repetition_penalty, sample)
+        self._check_options(temperature, top_k, top_p, repetition_penalty)
         self.prefill_chunk = prefill_chunk
         self.check_every = max(1, int(check_every))
         self.prefix_cache = prefix_cache
@@ -264,6 +281,12 @@ class ServingEngine:
         self.seen = torch.zeros(slots, V, dtype=torch.bool, device=dev)
         self.n_gen = torch.zeros(slots, dtype=torch.long, device=dev)
         self.limit_t = torch.zeros(slots, dtype=torch.long, device=dev)
+        # per-slot sampling options (empty slots are greedy: their token is discarded)
+        self.temp_t = torch.zeros(slots, dtype=torch.float32, device=dev)
+        self.top_k_t = torch.zeros(slots, dtype=torch.int32, device=dev)
+        self.top_p_t = torch.ones(slots, dtype=torch.float32, device=dev)
+        self.pen_t = torch.ones(slots, dtype=torch.float32, device=dev)
+        self.seed_t = torch.zeros(slots, dtype=torch.long, device=dev)
         self.out_buf = torch.zeros(slots, model.num_ctx, dtype=torch.long, device=dev)
         self._rows = torch.arange(slots, device=dev)
 
@@ -298,7 +321,33 @@ class ServingEngine:
 
     # ---- requests ----
 
-    def submit(self, prompt_tokens: Sequence[int], max_new_tokens: int) -> int:
+    @staticmethod
+    def _check_options(temperature, top_k, top_p, penalty) -> None:
+        if not (math.isfinite(temperature) and temperature >= 0):
+            raise ValueError(f"temperature {temperature}: need a finite value >= 0")
+        if top_k < 0:
+            raise ValueError(f"top_k {top_k}: need >= 0 (0 turns it off)")
+        if not 0 <= top_p <= 1:
+            raise ValueError(f"top_p {top_p}: need 0..1")
+        if not (math.isfinite(penalty) and penalty > 0):
+            raise ValueError(f"repetition_penalty {penalty}: need a finite value > 0")
+
+    def submit(self, prompt_tokens: Sequence[int], max_new_tokens: int, *,
+               sample: Optional[bool] = None, temperature: Optional[float] = None,
+               top_k: Optional[int] = None, top_p: Optional[float] = None,
+               repetition_penalty: Optional[float] = None,
+               seed: Optional[int] = None) -> int:
+        """Queue a request; None takes the constructor's value of an option.
+        Out-of-range options are a ValueError, like a request that can never
+        fit. `seed`: any integer (used modulo 2**64)."""
+        d_temp, d_k, d_p, d_pen, d_sample = self.sampling
+        temperature = float(d_temp if temperature is None else temperature)
+        top_k = int(d_k if top_k is None else top_k)
+        top_p = float(d_p if top_p is None else top_p)
+        penalty = float(d_pen if repetition_penalty is None else repetition_penalty)
+        self._check_options(temperature, top_k, top_p, penalty)
+        if not (d_sample if sample is None else sample):
+            temperature = 0.0
         prompt = [int(t) for t in prompt_tokens]
         n = len(prompt)
         if not 1 <= n <= self.model.num_ctx:
@@ -309,12 +358,17 @@ class ServingEngine:
             raise ValueError(
                 f"request needs {c.pages_for(n + limit)} pages of {c.page_rows} rows; "
                 f"the pool has {c.num_pages - 1}")
+        if seed is not None:
+            seed = (int(seed) + 2 ** 63) % 2 ** 64 - 2 ** 63  # as a signed 64-bit word
+        elif temperature > 0 and limit > 0:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         rid = self._next_id
         self._next_id += 1
         if limit <= 0:
             self.done[rid] = []
         else:
-            self.waiting.append(_Request(rid, prompt, limit))
+            self.waiting.append(_Request(rid, prompt, limit, temperature,
+                                         min(top_k, 2 ** 31 - 1), top_p, penalty, seed))
         return rid
 
     def idle(self) -> bool:
@@ -412,7 +466,7 @@ class ServingEngine:
             req.shared = len(shared)
             pages = c.assign(req.slot, n + req.limit, shared)
             self.running[req.slot] = req
-            self.info[req.rid] = dict(slot=req.slot, pages=pages,
+            self.info[req.rid] = dict(slot=req.slot, pages=pages, seed=req.seed,
                                       shared_pages=len(shared), start=len(shared) * R)
             batch.append(req)
             fresh_keys.update(k for k in req.keys if k not in self._page_of)
@@ -441,6 +495,12 @@ class ServingEngine:
         self.n_gen.index_fill_(0, sel, 0)
         self.cur.index_fill_(0, sel, 0)
         self.limit_t.index_copy_(0, sel, torch.tensor([r.limit for r in batch], device=dev))
+        for dst, vals in ((self.temp_t, [r.temperature for r in batch]),
+                          (self.top_k_t, [r.top_k for r in batch]),
+                          (self.top_p_t, [r.top_p for r in batch]),
+                          (self.pen_t, [r.penalty for r in batch]),
+                          (self.seed_t, [r.seed or 0 for r in batch])):
+            dst.index_copy_(0, sel, torch.tensor(vals, dtype=dst.dtype).to(dev))
         for r in batch:
             self._budget[r.slot] = r.limit
             # the prompt's full pages are valid for whoever is admitted later
@@ -458,7 +518,9 @@ class ServingEngine:
         return self.model(self.cur, static_cache=self.cache)
 
     def _sample_and_decode(self) -> None:
-        nxt = sample_batch(self.last, self.seen, *self.sampling)  # (slots,)
+        # token i of a request is drawn with u(seed, i): the counter is n_gen
+        nxt, _ = ops.sample_rows(self.last, self.seen, self.temp_t, self.top_k_t,
+                                 self.top_p_t, self.pen_t, self.seed_t, self.n_gen)
         emit = self.active.bool()
         if self.eos_token is not None:
             emit &= nxt != self.eos_token

@@ -476,6 +476,57 @@ def attention_decode_paged(
 
 
 # ---------------------------------------------------------------------------
+# Fused per-row sampler
+# ---------------------------------------------------------------------------
+
+SAMPLE_ROWS_MAX_V = 65536  # 1024 threads x 64 resident values (ops/csrc/sample.hip)
+
+
+def sample_rows(
+    logits: torch.Tensor, seen: Optional[torch.Tensor], temperature: torch.Tensor,
+    top_k: torch.Tensor, top_p: torch.Tensor, penalty: torch.Tensor,
+    seed: torch.Tensor, counter: torch.Tensor,
+):
+    """One token per row of logits (B, V), every option per row and on the
+    device -> (tokens (B,) int64, cut (B,) float32).
+
+    logits: fp16, bf16 or fp32, contiguous, never written. seen: (B, V) bool
+    as in sampling.apply_repetition_penalty_batched, or None. temperature,
+    top_p, penalty: (B,) float32; top_k: (B,) int32; seed, counter: (B,) int64,
+    all on the device of logits. Row b: repetition penalty on the seen tokens
+    (the bits apply_repetition_penalty_batched yields); temperature <= 0 takes
+    the lowest index of the maximum; otherwise top-k (0 or >= V: off; ties at
+    the k-th value are all kept), weights exp((y - max) / max(T, 1e-5)), top-p
+    as a threshold (the largest value whose upper mass exceeds p of the top-k
+    mass; values tied with it are all kept, which torch.sort-based
+    top_p_filter leaves to the sort order), and the first kept token, in
+    token order, whose inclusive mass exceeds u * the kept mass, with
+    u = uniform01(seed[b], counter[b]) of ops/csrc/common.h. `cut` is the
+    threshold used: the top-p cut, the k-th value when p >= 1 (-inf without
+    top-k), the maximum for a greedy row. The full definition is
+    reference.sample_rows, which is also the float64 oracle.
+
+    GPU: one HIP kernel (ops/csrc/sample.hip), one workgroup per row, no sort,
+    no host sync, nothing read on the host, bit-deterministic, so the call can
+    be captured in a graph and replayed with new options, seeds and counters
+    written on the device. It covers V <= 65536 (65536 - 7 for 16-bit logits,
+    65536 - 3 for fp32, when V * element size is no multiple of 16 bytes); a
+    larger V, and CPU tensors, take the reference."""
+    if not logits.is_cuda:
+        return reference.sample_rows(
+            logits, seen, temperature, top_k, top_p, penalty, seed, counter)
+    ext = hip_ops()
+    V, es = logits.shape[1], logits.element_size()
+    aligned = (V * es) % 16 == 0 and logits.data_ptr() % 16 == 0
+    if V + (0 if aligned else 16 // es - 1) > SAMPLE_ROWS_MAX_V:
+        return reference.sample_rows(
+            logits, seen, temperature, top_k, top_p, penalty, seed, counter)
+    tokens, cut = ext.sample_rows(
+        logits, seen, temperature, top_k, top_p, penalty, seed, counter)
+    return tokens, cut
+
+
+# ---------------------------------------------------------------------------
 # Fused residual-add + dropout:  y = x + dropout(h, p)
 # ---------------------------------------------------------------------------
 

@@ -34,6 +34,7 @@ SOURCES = [
     "attention_bwd.hip",
     "gemm_lt.hip",
     "gemv.hip",
+    "sample.hip",
 ]
 
 

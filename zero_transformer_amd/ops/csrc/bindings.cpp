@@ -41,6 +41,10 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor qkv, at::Tensor slo
                                  double p_drop, int64_t seed, int64_t fused);
 at::Tensor gemm_gelu(at::Tensor x, at::Tensor w);
 at::Tensor gemv(at::Tensor x, at::Tensor w);
+std::vector<at::Tensor> sample_rows(at::Tensor logits, c10::optional<at::Tensor> seen,
+                                    at::Tensor temperature, at::Tensor top_k,
+                                    at::Tensor top_p, at::Tensor penalty,
+                                    at::Tensor seed, at::Tensor counter);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("layernorm_fwd", &layernorm_fwd, "bias-free LayerNorm fwd (gfx950)");
@@ -78,4 +82,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_gelu", &gemm_gelu,
         "hipBLASLt x@w^T with fused GELU epilogue (no-grad path)");
   m.def("gemv", &gemv, "weight-streaming decode GEMV x@w^T (gfx950)");
+  m.def("sample_rows", &sample_rows,
+        "fused sort-free sampler, one workgroup per row, per-row options and "
+        "counter-based RNG -> {tokens, cut} (gfx950)");
 }

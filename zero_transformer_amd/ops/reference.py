@@ -307,6 +307,86 @@ def residual_drop_mask(seed: int, n: int, p: float) -> torch.Tensor:
     return torch.from_numpy(keep.copy())
 
 
+def uniform01(seed: int, counter: int) -> float:
+    """Python-integer mirror of csrc/common.h uniform01 (splitmix64 finalizer,
+    top 24 bits): the uniform in [0, 1) that the HIP sampler draws for
+    (seed, counter). Both are taken modulo 2**64."""
+    M = (1 << 64) - 1
+
+    def mix64(x):
+        x = (x + 0x9E3779B97F4A7C15) & M
+        x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & M
+        x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & M
+        return x ^ (x >> 31)
+
+    return (mix64((int(seed) & M) ^ mix64(int(counter) & M)) >> 40) / 16777216.0
+
+
+def sample_rows(logits, seen, temperature, top_k, top_p, penalty, seed, counter):
+    """The definition of ops.sample_rows in float64, one row at a time (the
+    oracle of the HIP sampler; also what CPU tensors take).
+
+    logits (B, V) float; seen (B, V) bool or None; temperature, top_p, penalty
+    (B,) float32; top_k (B,) int32; seed, counter (B,) int64 ->
+    (tokens (B,) int64, cut (B,) float32). Per row, with x = logits[b]:
+
+    1. penalty: where seen and penalty != 1, y = x / r if x > 0 else x * r,
+       computed and rounded as apply_repetition_penalty_batched does (in the
+       dtype of logits); otherwise y = x.
+    2. greedy (temperature <= 0): token = lowest index of max y, cut = max y.
+    3. top-k: kth = the k-th largest y, ties counted, if 0 < k < V, else -inf;
+       K = {y >= kth} (ties at kth are all kept).
+    4. weights w = exp((y - max y) / max(T, 1e-5)) on K.
+    5. top-p (p < 1): cut = the largest value v in y_K whose upper mass
+       sum{w : y >= v} exceeds p * sum_K w, else cut = kth; S = K & {y >= cut}
+       (values tied with the cut are all kept; never empty).
+    6. draw: u = uniform01(seed, counter); token = the smallest i in S, in
+       token order, whose inclusive mass over S exceeds u * sum_S w, or the
+       largest i in S if rounding leaves none.
+    """
+    B, V = logits.shape
+    toks = torch.zeros(B, dtype=torch.long)
+    cuts = torch.zeros(B, dtype=torch.float32)
+    neg_inf = float("-inf")
+    for b in range(B):
+        x = logits[b]
+        r = float(penalty[b])
+        if seen is not None and r != 1.0:
+            x = torch.where(seen[b], torch.where(x > 0, x / r, x * r), x)
+        y = x.detach().to("cpu", torch.float64)
+        y = torch.where(y.isnan(), torch.full_like(y, neg_inf), y)
+        m = float(y.max())
+        T = float(temperature[b])
+        if not T > 0.0:
+            toks[b], cuts[b] = int(y.argmax()), m
+            continue
+        k = int(top_k[b])
+        kth = float(torch.topk(y, k).values[-1]) if 0 < k < V else neg_inf
+        keep = y >= kth
+        w = torch.exp((y - m) / max(T, 1e-5)) * keep
+        cut = kth
+        p = max(float(top_p[b]), 0.0)
+        if p < 1.0:
+            ys, order = torch.sort(y[keep], descending=True)
+            upper = torch.cumsum(w[keep][order], 0)  # mass{y >= ys[j]} at a group's end
+            ends = torch.ones_like(ys, dtype=torch.bool)
+            ends[:-1] = ys[1:] != ys[:-1]
+            ok = ends & (upper > p * float(w.sum()))
+            if bool(ok.any()):
+                cut = max(float(ys[int(ok.nonzero()[0])]), kth)
+        in_s = keep & (y >= cut)
+        cdf = torch.cumsum(w * in_s, 0)
+        u = uniform01(int(seed[b]), int(counter[b]))
+        hit = (in_s & (cdf > u * float(cdf[-1]))).nonzero()
+        members = in_s.nonzero()
+        if hit.numel():
+            tok = int(hit[0])
+        else:
+            tok = int(members[-1]) if members.numel() else 0
+        toks[b], cuts[b] = min(max(tok, 0), V - 1), cut
+    return toks.to(logits.device), cuts.to(logits.device)
+
+
 def drop_inv_keep(p: float) -> float:
     """Rescale factor matching the kernels' realized 8-bit threshold."""
     thr = int(p * 256.0 + 0.5)
