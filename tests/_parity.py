@@ -1,6 +1,6 @@
 """Float64 references and one derived error bound for the HIP kernel parity
-tests (tests/test_gpu_ops_edges.py, checked on CPU by
-tests/test_parity_helpers.py).
+tests (tests/test_gpu_ops_edges.py, tests/test_gpu_attn_bwd_edges.py, checked
+on CPU by tests/test_parity_helpers.py).
 
 Every reference is computed in float64 from the exact bf16 / fp16 / fp32
 values the kernel receives. The one checker is
@@ -19,7 +19,8 @@ values the kernel receives. The one checker is
   says where it comes from.
 
 The bounds are derived from the formats and the formulas, never fitted to
-what a kernel returns.
+what a kernel returns. (The training attention's o and lse keep the absolute
+bounds of tests/test_gpu_attn_fwd_edges.py instead: see attn_bwd_ref.)
 """
 
 from __future__ import annotations
@@ -391,3 +392,130 @@ def attn_decode_ref(q, k, v, slopes, s_used=None):
     p = torch.softmax(scores, -1)
     ds = ACC * mag.amax(-1, keepdim=True)
     return p @ V, (ACC + 2.0 * ds) * (p @ V.abs())
+
+
+# ---------------------------------------------------------------------------
+# Training attention, forward + backward (causal, ALiBi, dropout on P)
+# ---------------------------------------------------------------------------
+
+U_BF16 = 2.0 ** -8  # half an ulp: relative error of one rounding to bf16
+# o / lse: the absolute bounds of tests/test_gpu_attn_fwd_edges.py
+ATTN_O_TOL = 3e-2
+ATTN_O_TOL_MASK = 4e-2
+ATTN_LSE_TOL = 1e-4
+
+ATTN_BH = (2, 3)
+ATTN_SEED = 12345
+ATTN_T = (40, 65, 129, 257, 320)
+# (T, D, p, q/k scale, alibi): see the table in test_gpu_attn_bwd_edges.py
+ATTN_BWD_TWO = (
+    [(T, D, 0.0, 1.0, True) for D in (32, 64, 96, 128) for T in ATTN_T]
+    + [(T, D, 0.3, 1.0, True) for D in (32, 64, 96, 128) for T in (65, 257)]
+    + [(129, 96, 0.1, 1.0, True)]
+)
+ATTN_BWD_FUSED = (
+    [(T, 128, 0.0, 1.0, True) for T in (40, 65, 257, 320, 576)]
+    + [(T, 128, 0.3, 1.0, True) for T in (65, 257, 576)]
+)
+ATTN_BWD_BIG = [(320, 128, 0.0, 4.0, True), (320, 128, 0.0, 4.0, False)]
+# (B, H, T, D): rows = B * H * T just past one pass of each delta kernel
+ATTN_DELTA_STRIDE = [(1, 8, 1040, 32), (4, 16, 1040, 64)]
+
+
+def attn_bwd_inputs(B, H, T, D, qk_scale=1.0):
+    """q, k, v, do as (B, H, T, D) bf16, fixed per shape and scale."""
+    seed = 7000 + 8 * (T * 131 + D) + (4 if qk_scale != 1.0 else 0)
+    q = randn((B, H, T, D), BF16, seed, qk_scale)
+    k = randn((B, H, T, D), BF16, seed + 1, qk_scale)
+    v = randn((B, H, T, D), BF16, seed + 2)
+    do = randn((B, H, T, D), BF16, seed + 3)
+    return q, k, v, do
+
+
+def worst_abs_ratio(got, want, tol) -> float:
+    """max |got - want| / tol (inf if not finite or shapes differ)."""
+    g, w = f64(got), f64(want)
+    if g.shape != w.shape:
+        return math.inf
+    ratio = torch.nan_to_num((g - w).abs() / tol, nan=math.inf, posinf=math.inf)
+    return float(ratio.max())
+
+
+def attn_bwd_ref(q, k, v, do, slopes, keep=None, inv_keep=1.0):
+    """q, k, v, do (B, H, T, D); slopes (H,) or None; keep bool (B, H, T, T) or
+    None. -> {name: (want, abs_term)} for o, lse, dq, dk, dv, each (B, H, T, D)
+    (lse (B, H, T)). Closed formulas in float64, no autograd:
+
+        S = scale Q K^T + slope (j - i), causal;   P = softmax(S)
+        Pd = P keep inv_keep;          O = Pd V
+        dPd = (dO V^T) keep inv_keep;  delta = rowsum(P dPd)  (= rowsum(dO O))
+        dS = scale P (dPd - delta)
+        dV = Pd^T dO;   dQ = dS K;   dK = dS^T Q
+
+    o and lse carry the forward edge tests' ABSOLUTE bounds as abs_term (3e-2,
+    4e-2 with a mask; 1e-4) and are checked with worst_abs_ratio, so they are
+    no wider here than there. dq, dk, dv go through worst_ratio; their
+    abs_term follows from what the kernels (ops/csrc/attention_bwd.hip) round,
+    with u = 2^-8 one rounding to bf16:
+
+    * p is recomputed in fp32 as exp2(s scale2 + slope2 (j - i) - lse2) from
+      the forward's lse. An absolute error e of the exponent is a relative
+      error e of p: the saved lse gives ATTN_LSE_TOL, the fp32 score sum and
+      the two fp32 additions give ACC x (scale (|Q||K|^T)_ij + |bias_ij|).
+      (The bias magnitude is not in the issue's list; it is the other operand
+      of the same fp32 sum, as in attn_decode_ref.)
+          eps_ij = 1e-4 + ACC (scale (|Q||K|^T)_ij + |slope (j - i)|)
+    * Pd is rounded to bf16 for its MFMA:  dv: ((u + eps) |Pd|)^T |dO|
+    * delta = rowsum(dO O) reads the bf16 O of the forward (u |O|), which the
+      forward formed from bf16-rounded P (another u (|Pd||V|)):
+          E_delta_i = 2u sum_d |dO_id| (|Pd||V|)_id
+    * dP is an fp32 sum of D products: E_dP = ACC (|dO||V|^T) keep inv_keep
+      (also not in the issue's list; a few per cent of the u term).
+    * dS is rounded to bf16 for its MFMAs:
+          E_dS = (u + eps) |dS| + scale P (E_delta + E_dP)
+                 + eps scale P (|dPd| + |delta|)
+      dq: E_dS |K|;   dk: E_dS^T |Q|.
+    The fp32 accumulation of the three output products (ACC x the same sums of
+    |terms|) is far below their u terms and is covered by eps >= 1e-4; the
+    fused kernel's f32 atomics add dQ partial sums in fp32 likewise.
+    Nothing here is fitted to what a kernel returns.
+    """
+    Q, K, V, DO = f64(q), f64(k), f64(v), f64(do)
+    B, H, T, D = Q.shape
+    sc = 1.0 / math.sqrt(D)
+    S = (Q @ K.transpose(-1, -2)) * sc
+    mag = (Q.abs() @ K.abs().transpose(-1, -2)) * sc
+    if slopes is not None:
+        pos = torch.arange(T, dtype=torch.float64)
+        bias = f64(slopes).view(1, H, 1, 1) * (pos.view(1, T) - pos.view(T, 1))
+        S = S + bias
+        mag = mag + bias.abs()
+    causal = torch.ones(T, T, dtype=torch.bool).tril()
+    S = S.masked_fill(~causal, -math.inf)
+    lse = torch.logsumexp(S, -1)
+    P = torch.exp(S - lse[..., None])
+    if keep is None:
+        km = torch.ones((), dtype=torch.float64)
+    else:
+        km = keep.cpu().double() * float(np.float32(inv_keep))
+    Pd = P * km
+    O = Pd @ V
+    dPd = (DO @ V.transpose(-1, -2)) * km
+    delta = (P * dPd).sum(-1, keepdim=True)
+    dS = sc * P * (dPd - delta)
+    dV = Pd.transpose(-1, -2) @ DO
+    dQ = dS @ K
+    dK = dS.transpose(-1, -2) @ Q
+
+    u = U_BF16
+    eps = ATTN_LSE_TOL + ACC * mag
+    e_delta = 2.0 * u * (DO.abs() * (Pd.abs() @ V.abs())).sum(-1, keepdim=True)
+    e_dp = ACC * (DO.abs() @ V.abs().transpose(-1, -2)) * km
+    e_ds = (u + eps) * dS.abs() + sc * P * (e_delta + e_dp) + eps * sc * P * (dPd.abs() + delta.abs())
+    return {
+        "o": (O, ATTN_O_TOL if keep is None else ATTN_O_TOL_MASK),
+        "lse": (lse, ATTN_LSE_TOL),
+        "dq": (dQ, e_ds @ K.abs()),
+        "dk": (dK, e_ds.transpose(-1, -2) @ Q.abs()),
+        "dv": (dV, ((u + eps) * Pd.abs()).transpose(-1, -2) @ DO.abs()),
+    }

@@ -2,9 +2,11 @@
 
 (a) The bounds are not too tight: the project's fp32 reference ops and an
     fp32 emulation of the kernels' own formulas (E[x^2] - mean^2 variance,
-    exp(x - lse) gradient, x * sigmoid(2u) GELU), rounded to the output type,
-    pass at every shape the GPU tests use.
-(b) The bounds have power: three deliberately wrong results fail.
+    exp(x - lse) gradient, x * sigmoid(2u) GELU, attention backward with its
+    bf16 roundings of O, Pd and dS), rounded to the output type, pass at
+    every shape the GPU tests use.
+(b) The bounds have power: deliberately wrong results fail (three for the
+    row kernels, five for attention backward).
 """
 
 import math
@@ -73,6 +75,65 @@ def gelu_emul(x, dy):
     sech2 = 4.0 * sg * (1.0 - sg)
     grad = sg + 0.5 * X * sech2 * k0 * (1.0 + 3.0 * k1 * x2)
     return (X * sg).to(x.dtype), (DY * grad).to(x.dtype)
+
+
+def attn_bwd_emul(q, k, v, do, slopes, keep, inv_keep, inject=None):
+    """The attention kernels' formulas in fp32 with exactly their roundings:
+    O, Pd and dS through bf16 before they are used, outputs to bf16.
+    -> dq, dk, dv, o, lse. `inject` applies one deliberate error to the
+    BACKWARD (the forward's o and lse stay right):
+      "row"   dS of the last query row zeroed
+      "keep"  keep bits of the last 4 keys of the last query row flipped
+      "delta" delta summed over the first D - 8 columns
+      "p"     p scaled by 1.01
+      "alibi" bias one position off for the keys of the last 64-key tile
+    """
+    Q, K, V, DO = q.float(), k.float(), v.float(), do.float()
+    B, H, T, D = Q.shape
+    sc = torch.tensor(1.0 / math.sqrt(D), dtype=torch.float32)
+    pos = torch.arange(T, dtype=torch.float32)
+    rel = pos.view(1, T) - pos.view(T, 1)
+    sl = (torch.zeros(H) if slopes is None else slopes.float()).view(1, H, 1, 1)
+    causal = torch.ones(T, T, dtype=torch.bool).tril()
+    QK = (Q @ K.transpose(-1, -2)) * sc
+    S = (QK + sl * rel).masked_fill(~causal, -math.inf)
+    lse = torch.logsumexp(S, -1)
+    km = torch.ones(()) if keep is None else keep.float() * torch.tensor(inv_keep, dtype=torch.float32)
+    O = ((torch.exp(S - lse[..., None]) * km).to(BF16).float() @ V).to(BF16)
+
+    if inject == "alibi":
+        rel = rel + (pos >= 64 * ((T - 1) // 64)).float().view(1, T)
+        S = (QK + sl * rel).masked_fill(~causal, -math.inf)
+    p = torch.exp(S - lse[..., None])
+    if inject == "p":
+        p = p * 1.01
+    if inject == "keep":
+        km = km.clone()
+        km[..., -1, -4:] = (~keep[..., -1, -4:]).float() * torch.tensor(inv_keep, dtype=torch.float32)
+    Pd = (p * km).to(BF16).float()
+    dPd = (DO @ V.transpose(-1, -2)) * km
+    cols = D - 8 if inject == "delta" else D
+    delta = (DO[..., :cols] * O.float()[..., :cols]).sum(-1, keepdim=True)
+    dS = sc * p * (dPd - delta)
+    if inject == "row":
+        dS[..., -1, :] = 0.0
+    dS = dS.to(BF16).float()
+    return {
+        "dq": (dS @ K).to(BF16),
+        "dk": (dS.transpose(-1, -2) @ Q).to(BF16),
+        "dv": (Pd.transpose(-1, -2) @ DO).to(BF16),
+        "o": O,
+        "lse": lse,
+    }
+
+
+def _attn_case(T, D, p, qk_scale=1.0, alibi=True):
+    B, H = P.ATTN_BH
+    q, k, v, do = P.attn_bwd_inputs(B, H, T, D, qk_scale)
+    slopes = reference.alibi_slopes(H) if alibi else None
+    keep = reference.drop_mask(P.ATTN_SEED, B, H, T, p) if p > 0 else None
+    inv = reference.drop_inv_keep(p)
+    return (q, k, v, do, slopes, keep, inv), P.attn_bwd_ref(q, k, v, do, slopes, keep, inv)
 
 
 def _check_all(got, want, dtype, names, tag):
@@ -203,9 +264,67 @@ def test_gemv_and_decode_bounds_admit_fp32(dtype):
         P.assert_within(got, want, dtype, a, f"decode D={D} S={S}")
 
 
+_ATTN_SHAPES = sorted(set(P.ATTN_BWD_TWO + P.ATTN_BWD_FUSED + P.ATTN_BWD_BIG))
+_ATTN_WORST = {}
+
+
+def _attn_emul_check(args, want, tag):
+    got = attn_bwd_emul(*args)
+    assert all(torch.isfinite(t.float()).all() for t in got.values())
+    for n in ("o", "lse"):
+        r = P.worst_abs_ratio(got[n], *want[n])
+        print(f"[parity] {tag} {n}: worst error/bound = {r:.3f}")
+        assert r <= 1.0
+    for n in ("dq", "dk", "dv"):
+        P.assert_within(got[n], want[n][0], BF16, want[n][1], f"attn-emul-{n} {tag}", _ATTN_WORST)
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _attn_summary():
+    yield
+    for op, r in sorted(_ATTN_WORST.items()):
+        print(f"[parity-summary] {op}: worst error/bound = {r:.3f}")
+
+
+@pytest.mark.parametrize("T,D,p,qk_scale,alibi", _ATTN_SHAPES)
+def test_attn_bwd_bounds_admit_emulation(T, D, p, qk_scale, alibi):
+    """Every (T, D, p, scale) of test_gpu_attn_bwd_edges.py: the fp32
+    emulation with the kernels' bf16 roundings stays within the bound."""
+    args, want = _attn_case(T, D, p, qk_scale, alibi)
+    _attn_emul_check(args, want, f"T={T} D={D} p={p} x{qk_scale:g} alibi={int(alibi)}")
+
+
+@pytest.mark.parametrize("B,H,T,D", P.ATTN_DELTA_STRIDE)
+def test_attn_bwd_bounds_admit_emulation_long(B, H, T, D):
+    """The delta grid-stride shapes, on the two (b, h) planes the GPU test
+    checks (the first and the last)."""
+    q, k, v, do = P.attn_bwd_inputs(B, H, T, D)
+    slopes = reference.alibi_slopes(H)
+    for b, h in ((0, 0), (B - 1, H - 1)):
+        cut = lambda t: t[b:b + 1, h:h + 1]
+        args = (cut(q), cut(k), cut(v), cut(do), slopes[h:h + 1], None, 1.0)
+        _attn_emul_check(args, P.attn_bwd_ref(*args), f"T={T} D={D} plane=({b},{h})")
+
+
 # ---------------------------------------------------------------------------
 # (b) power
 # ---------------------------------------------------------------------------
+
+
+@pytest.fixture(scope="module", params=[(300, 128, 0.3), (257, 96, 0.1)], ids=str)
+def attn_power_case(request):
+    return _attn_case(*request.param)
+
+
+@pytest.mark.parametrize("inject", ["row", "keep", "delta", "p", "alibi"])
+def test_bound_rejects_wrong_attention_backward(attn_power_case, inject):
+    """Five errors a tile-edge or indexing bug would make; each must exceed
+    the bound on at least one of dq / dk / dv."""
+    args, want = attn_power_case
+    bad = attn_bwd_emul(*args, inject=inject)
+    r = {n: P.worst_ratio(bad[n], want[n][0], BF16, want[n][1]) for n in ("dq", "dk", "dv")}
+    print(f"[parity] inject {inject}: " + " ".join(f"{n}={v:.2f}" for n, v in r.items()))
+    assert max(r.values()) > 1.0, f"{inject} passed: {r}"
 
 
 @pytest.mark.parametrize("C,whole", [(768, 512), (1280, 1024)])

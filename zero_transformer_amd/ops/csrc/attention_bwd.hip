@@ -850,11 +850,38 @@ inline bool bwd_fused_default() {
 std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor qkv, at::Tensor slopes,
                                  at::Tensor o, at::Tensor lse, int64_t H_,
                                  double p_drop, int64_t seed, int64_t fused) {
-  TORCH_CHECK(qkv.is_cuda() && qkv.is_contiguous() && qkv.dim() == 3);
-  TORCH_CHECK(dout.is_contiguous() && dout.dim() == 3);
+  // Everything the kernels take on trust is checked here, before any launch:
+  // they reinterpret the buffers as bf16 / f32 bits and index them by
+  // (B, T, C) and (B, H, T) alone.
+  TORCH_CHECK(qkv.is_cuda() && qkv.is_contiguous() && qkv.dim() == 3,
+              "attn_bwd: qkv must be (B, T, 3C) contiguous on the GPU");
+  TORCH_CHECK(qkv.scalar_type() == at::kBFloat16, "attn_bwd: qkv must be bf16");
+  TORCH_CHECK(H_ > 0, "attn_bwd: H must be positive, got ", H_);
   const int B = qkv.size(0), T = qkv.size(1), H = (int)H_;
   const int C = qkv.size(2) / 3;
+  TORCH_CHECK(qkv.size(2) == 3 * C && C % H == 0,
+              "attn_bwd: qkv last dim must be 3C with C % H == 0, got ", qkv.size(2),
+              " for H = ", H);
   const int D = C / H;
+  TORCH_CHECK(D == 32 || D == 64 || D == 96 || D == 128,
+              "attn_bwd: head_dim must be 32/64/96/128, got ", D);
+  auto check_act = [&](const at::Tensor& t, const char* name) {
+    TORCH_CHECK(t.device() == qkv.device(), "attn_bwd: ", name, " must be on qkv's device");
+    TORCH_CHECK(t.scalar_type() == at::kBFloat16, "attn_bwd: ", name, " must be bf16");
+    TORCH_CHECK(t.dim() == 3 && t.size(0) == B && t.size(1) == T && t.size(2) == C,
+                "attn_bwd: ", name, " must be (B, T, C)");
+    TORCH_CHECK(t.is_contiguous(), "attn_bwd: ", name, " must be contiguous");
+  };
+  check_act(dout, "dout");
+  check_act(o, "o");
+  TORCH_CHECK(lse.device() == qkv.device(), "attn_bwd: lse must be on qkv's device");
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.dim() == 3 && lse.size(0) == B &&
+                  lse.size(1) == H && lse.size(2) == T,
+              "attn_bwd: lse must be float32 (B, H, T)");
+  TORCH_CHECK(lse.is_contiguous(), "attn_bwd: lse must be contiguous");
+  TORCH_CHECK(slopes.device() == qkv.device(), "attn_bwd: slopes must be on qkv's device");
+  TORCH_CHECK(slopes.numel() == H, "attn_bwd: slopes must have H = ", H,
+              " elements, got ", slopes.numel());
   auto dqkv = at::empty_like(qkv);
   auto delta = at::empty({B, H, T}, qkv.options().dtype(at::kFloat));
   auto sl = slopes.to(at::kFloat).contiguous();
