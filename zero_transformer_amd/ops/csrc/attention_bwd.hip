@@ -466,6 +466,18 @@ __global__ __launch_bounds__(256, 1) void flash_dkdv4_kernel(
 // reads of the dS tile, B = transpose reads of the block's K image) and
 // adds it into the f32 scratch with no-return atomics: one accumulator
 // register is two 128 B row segments. No workgroup waits on another.
+// Softmax: the lane's 16 rows of lse and delta are read once per slice as
+// 4 + 4 16-byte LDS reads ahead of the MFMAs and shared by both key groups;
+// lse * log2e and the row part of the ALiBi term fold into one row constant,
+// the key part is one lane constant per group. Two variants, chosen per
+// slice by a wave-uniform branch around the softmax only (as dropout on /
+// off is): INTERIOR when every one of the wave's 64 keys is at or below
+// every row of the slice and the slice lies below T (no compare, no select;
+// at least 7 of 9 slices at T = 2048), MASKED for diagonal and tail slices (exponent
+// computed unconditionally, then selected to 0: no divergent region).
+// Dropout: the four lanes of a quad own four keys of one drop_bits32 word
+// and the same 16 rows, so each hashes 4 of the 16 rows and the quad
+// exchanges the words by DPP quad_perm; every lane keeps its own byte.
 // LDS: K image 256x[256B] | q0 do0 q1 do1 32x[256B] | dS 2x 256x[64B] |
 //      (lse, delta) 2x 64 f32 = 128.5 KiB. No vector-memory load inside the
 // slice loop returns to a register (Q, dO, lse and delta all arrive by
@@ -596,6 +608,27 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_fused_kernel(
       // K rows come from the K image, V fragments are resident.
       attn::TrQuad qq[2];
       bf16x8 pa[2][2], dsa[2][2];
+      // Row statistics of the lane's 16 rows (four runs of four consecutive
+      // floats), read once ahead of the MFMAs and shared by both key groups:
+      // rowc = lse * log2e + slope2 * row (the row part of the ALiBi term
+      // folded into the exponent's row constant) and delta.
+      float rowc[16], dlt[16];
+      {
+        const float srow0 = slope2 * (float)(4 * hi);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const f32x4 l4 = *reinterpret_cast<const f32x4*>(lse_s + 8 * j + 4 * hi);
+          const f32x4 d4 = *reinterpret_cast<const f32x4*>(delta_s + 8 * j + 4 * hi);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            rowc[4 * j + i] = l4[i] * LOG2E + (slope2 * (float)(8 * j + i) + srow0);
+            dlt[4 * j + i] = d4[i];
+          }
+        }
+      }
+      // No element of this wave's 64 keys x 32 rows is masked: every key is
+      // at or below every row and the slice lies wholly below T.
+      const bool interior = kw + 63 <= q32 && q32 + FQS <= T;
 #pragma unroll
       for (int g = 0; g < 2; ++g) {
         // S = Q K^T ; dP = dO V^T  (C[i=q][j=key])
@@ -626,43 +659,78 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_fused_kernel(
 
         float p_pv[16], ds[16];
         const int kj = kw + 32 * g + li;
-        auto softmax = [&](auto drop) {
-          // drop_bits32 with its row term formed incrementally (uint32 wrap
-          // arithmetic, bit-identical): (bh*T + q32 + row) * 0x9e3779b9
-          const uint32_t hrow0 = (uint32_t)(bh * T + q32 + 4 * hi) * 0x9e3779b9u;
-          const uint32_t hkey = seed ^ ((uint32_t)(kj >> 2) * 0x85ebca6bu);
-          const int kshift = 8 * (kj & 3);
+        // exponent = s*scale2 + slope2*(kj - qi) - lse2 with the ALiBi term
+        // split as slope2*(kj - q32) (one lane constant per group, the
+        // integer difference exact) minus the row part held in rowc.
+        const int kd = kj - q32;
+        const float akey = slope2 * (float)kd;
+        auto softmax = [&](auto drop, auto mask) {
+          // Row r = 4j + i of the lane is slice row 8j + i + 4*hi (literal
+          // attn::crow, as at the dQ atomics and the epilogue below: with the
+          // helper the same values come out of a different instruction
+          // schedule, which nobody has timed).
+          // Masked variant: row is masked iff kj > qi, kj >= T or qi >= T,
+          // i.e. 8j + i < mlo or 8j + i >= mhi with the lane's 4*hi taken out.
+          const int mlo = (kj < T ? kd : 2 * FQS) - 4 * hi;
+          const int mhi = T - q32 - 4 * hi;
+          // Dropout: the four lanes of a quad hold four keys of one key quad
+          // and the same 16 rows, so they need the same 16 drop_bits32 words
+          // and each keeps another byte. Quad lane ql hashes the rows of run
+          // j = ql; every lane then takes run j's words from quad lane j by
+          // DPP. The row term is formed incrementally (uint32 wrap
+          // arithmetic, bit-identical): (bh*T + q32 + row) * 0x9e3779b9.
+          uint32_t hq[4] = {};
+          const int kshift = 8 * (lv & 3);  // = 8 * (kj & 3)
+          if (decltype(drop)::value) {
+            const uint32_t hrow =
+                (uint32_t)(bh * T + q32 + 4 * hi + 8 * (lv & 3)) * 0x9e3779b9u;
+            const uint32_t hkey = seed ^ ((uint32_t)(kj >> 2) * 0x85ebca6bu);
 #pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            // attn::crow(r, hi), spelled out in this kernel (here and at the
-            // dQ atomics and the epilogue below): with the helper the same
-            // values come out of a different instruction schedule (at the
-            // two sums even 8049 -> 8077 instructions), which nobody has timed.
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * hi;
-            const int qi = q32 + row;
-            const float lq = lse_s[row] * LOG2E;  // log2 domain
-            const float dq_ = delta_s[row];
-            const bool masked = kj > qi || kj >= T || qi >= T;
-            const float x = masked ? -3.0e38f
-                                   : s_acc[r] * scale2 + slope2 * (float)(kj - qi) - lq;
-            const float p = __builtin_amdgcn_exp2f(x);  // raw v_exp_f32; exp2(-3e38) = 0
-            float dp = dp_acc[r];
-            float ppv = p;
-            if (decltype(drop)::value) {
-              const uint32_t bits =
-                  mix32(hkey ^ (hrow0 + (uint32_t)((r & 3) + 8 * (r >> 2)) * 0x9e3779b9u));
-              const bool keep = ((bits >> kshift) & 0xffu) >= thr;
-              dp = keep ? dp * inv_keep : 0.f;
-              ppv = keep ? p * inv_keep : 0.f;
-            }
-            p_pv[r] = ppv;
-            ds[r] = scale * p * (dp - dq_);
+            for (int i = 0; i < 4; ++i) hq[i] = mix32(hkey ^ (hrow + (uint32_t)i * 0x9e3779b9u));
           }
+          auto run = [&](auto jc) {
+            constexpr int j = decltype(jc)::value;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              const int r = 4 * j + i;
+              const float x = (s_acc[r] * scale2 + akey) - rowc[r];
+              float p = __builtin_amdgcn_exp2f(x);  // raw v_exp_f32
+              if (decltype(mask)::value) {
+                // computed unconditionally, then selected: no divergent region
+                const bool masked = 8 * j + i < mlo || 8 * j + i >= mhi;
+                p = masked ? 0.f : p;
+              }
+              float dp = dp_acc[r];
+              float ppv = p;
+              if (decltype(drop)::value) {
+                const uint32_t bits = (uint32_t)__builtin_amdgcn_update_dpp(
+                    0, (int)hq[i], j * 0x55 /* quad_perm:[j,j,j,j] */, 0xf, 0xf, true);
+                const bool keep = ((bits >> kshift) & 0xffu) >= thr;
+                dp = keep ? dp * inv_keep : 0.f;
+                ppv = keep ? p * inv_keep : 0.f;
+              }
+              p_pv[r] = ppv;
+              ds[r] = scale * p * (dp - dlt[r]);
+            }
+          };
+          run(std::integral_constant<int, 0>{});
+          run(std::integral_constant<int, 1>{});
+          run(std::integral_constant<int, 2>{});
+          run(std::integral_constant<int, 3>{});
         };
-        if (thr)
-          softmax(std::true_type{});
-        else
-          softmax(std::false_type{});
+        // Wave-uniform branches around the softmax only (never around an
+        // accumulation): dropout on / off, masked / interior.
+        if (thr) {
+          if (interior)
+            softmax(std::true_type{}, std::false_type{});
+          else
+            softmax(std::true_type{}, std::true_type{});
+        } else {
+          if (interior)
+            softmax(std::false_type{}, std::false_type{});
+          else
+            softmax(std::false_type{}, std::true_type{});
+        }
         c_to_a_frags(p_pv, pa[g]);  // A[i=key][k=q]
         c_to_a_frags(ds, dsa[g]);
         // the same words are the dS tile's [key][q] rows: 16 B per lane
@@ -702,20 +770,26 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_fused_kernel(
     const int nkp = min(kend64, (q32 + 32 - k0 + 63) & ~63) >> 5;  // even, >= 2
     f32x16 dq = f32x16{};
     attn::TrQuad kq[2];
+    // The last trip is peeled so that no read in flight meets an if / else
+    // join: joined there, the compiler may place the register copies of the
+    // join ahead of the wait on one side (it cannot see the reads inside
+    // the asm) and copy fragments that have not arrived.
     attn::tr_dsk_issue(ds_t, k_img, 0, 32 * wave, &kq[0], lv);
+    int kp = 0;
 #pragma unroll 1
-    for (int kp = 0; kp < nkp; kp += 2) {
+    for (; kp + 2 < nkp; kp += 2) {
       attn::tr_dsk_issue(ds_t, k_img, (kp + 1) * 32, 32 * wave, &kq[1], lv);
       attn::tr_quad_wait<8>(&kq[0]);
       attn::mfma_quad_acc(dq, kq[0]);
-      if (kp + 2 < nkp) {
-        attn::tr_dsk_issue(ds_t, k_img, (kp + 2) * 32, 32 * wave, &kq[0], lv);
-        attn::tr_quad_wait<8>(&kq[1]);
-      } else {
-        attn::tr_quad_wait<0>(&kq[1]);
-      }
+      attn::tr_dsk_issue(ds_t, k_img, (kp + 2) * 32, 32 * wave, &kq[0], lv);
+      attn::tr_quad_wait<8>(&kq[1]);
       attn::mfma_quad_acc(dq, kq[1]);
     }
+    attn::tr_dsk_issue(ds_t, k_img, (kp + 1) * 32, 32 * wave, &kq[1], lv);
+    attn::tr_quad_wait<8>(&kq[0]);
+    attn::mfma_quad_acc(dq, kq[0]);
+    attn::tr_quad_wait<0>(&kq[1]);
+    attn::mfma_quad_acc(dq, kq[1]);
     // one register = rows crow(r,0) and crow(r,1), 128 B each; left in flight
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
