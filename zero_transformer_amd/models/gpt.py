@@ -121,14 +121,31 @@ class Block(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         # residual adds with the reference's resid/MLP dropout fused in
-        # (dropout(h) then add, layers.py:76,190 + GPT.py:43-49)
-        x = ops.residual_dropout_add(
-            x, self.attn(self.ln1(x)), self.dropout_p, self.training
+        # (dropout(h) then add, layers.py:76,190 + GPT.py:43-49); the first
+        # add also yields ln2 of its result from the same kernel
+        x, ln_x = self._attn_half(x, self.ln1(x))
+        return ops.residual_dropout_add(
+            x, self.mlp(ln_x), self.dropout_p, self.training
         )
-        x = ops.residual_dropout_add(
-            x, self.mlp(self.ln2(x)), self.dropout_p, self.training
+
+    def _attn_half(self, x: torch.Tensor, ln_x: torch.Tensor):
+        """(x, ln1(x)) -> (x', ln2(x')), x' = x + dropout(attn(ln1(x)))."""
+        return ops.residual_dropout_add_ln(
+            x, self.attn(ln_x), self.dropout_p, self.training,
+            self.ln2.weight, self.ln2.eps,
         )
-        return x
+
+    def forward_pair(self, x: torch.Tensor, ln_x: torch.Tensor, next_norm: LayerNorm):
+        """The block on the carried pair (x, ln_x = ln1(x)) -> (x_out,
+        next_norm(x_out)): each residual add is fused with the LayerNorm
+        that reads its result (ln2; then the next block's ln1, or the
+        model's final norm). The LayerNorm modules' weights are read
+        directly: forward hooks on ln2 or on next_norm do not fire."""
+        x, ln_x = self._attn_half(x, ln_x)
+        return ops.residual_dropout_add_ln(
+            x, self.mlp(ln_x), self.dropout_p, self.training,
+            next_norm.weight, next_norm.eps,
+        )
 
 
 class GPT(nn.Module):
@@ -163,9 +180,17 @@ class GPT(nn.Module):
         labels: Optional[torch.Tensor] = None,
     ) -> Union[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]]:
         x = self.wte(idx)
-        for block in self.blocks:
-            x = block(x)
-        x = self.norm(x)
+        # carry (x, LN(x)) from block to block, as the decode path of
+        # models/inference.py does: only the first LayerNorm is a kernel of
+        # its own. Blocks run through forward_pair, not Block.__call__, and
+        # the later LayerNorms through their weights: module forward hooks on
+        # blocks, ln2, later ln1 and the final norm do not fire here (attn
+        # and mlp are still called as modules).
+        norms = [b.ln1 for b in self.blocks] + [self.norm]
+        ln_x = norms[0](x)
+        for i, block in enumerate(self.blocks):
+            x, ln_x = block.forward_pair(x, ln_x, norms[i + 1])
+        x = ln_x
         logits = F.linear(x, self.lm_head.weight)
         if labels is None:
             return logits

@@ -83,8 +83,20 @@ class _LinearFn(torch.autograd.Function):
         x, w = ctx.saved_tensors
         dy = dy.contiguous()
         dx = dy @ w
-        dw = dy.reshape(-1, dy.shape[-1]).T @ x.reshape(-1, x.shape[-1])
-        return dx, dw
+        dy2 = dy.reshape(-1, dy.shape[-1]).T
+        x2 = x.reshape(-1, x.shape[-1])
+        # A ZeRO1Optimizer hangs `_zta_grad_sink` on the parameters it owns:
+        # it hands out the parameter's view of the flat gradient bucket for
+        # the first gradient of a step, and the GEMM writes there instead of
+        # into a temporary that would then be copied (same GEMM, same shapes
+        # and layouts, only the output pointer differs).
+        sink = getattr(w, "_zta_grad_sink", None)
+        view = sink.first_grad_view(w) if sink is not None else None
+        if view is None or view.dtype != dy2.dtype:
+            return dx, dy2 @ x2
+        torch.mm(dy2, x2, out=view)
+        sink.grad_written(w)
+        return dx, None
 
 
 def linear(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
@@ -562,6 +574,78 @@ def residual_dropout_add(
 
 
 # ---------------------------------------------------------------------------
+# Fused residual-add + dropout + LayerNorm:  x' = x + dropout(h, p),
+# y = LN(x') * w
+# ---------------------------------------------------------------------------
+
+
+class _ResidualDropoutLnFn(torch.autograd.Function):
+    """(x, h, w) -> (x', y). One kernel forward; one kernel backward that
+    takes the LayerNorm gradient, adds what arrives at x' from further down
+    the residual stream and masks the sum for h. Bit-identical to
+    residual_dropout_add followed by layer_norm, forward and backward."""
+
+    @staticmethod
+    def forward(ctx, x, h, w, p, training, eps):
+        ext = hip_ops()
+        if p > 0.0 and training:
+            seed = _next_dropout_seed()
+        else:
+            seed, p = 0, 0.0
+        xp, y, rstd, mean = ext.residual_ln_fwd(
+            x.contiguous(), h.contiguous(), w.contiguous(), float(p), seed, eps
+        )
+        ctx.save_for_backward(xp, w, rstd, mean)
+        ctx.p = p
+        ctx.seed = seed
+        # an output nobody used arrives as None, not as a tensor of zeros
+        ctx.set_materialize_grads(False)
+        return xp, y
+
+    @staticmethod
+    def backward(ctx, dxp, dy):
+        xp, w, rstd, mean = ctx.saved_tensors
+        if dy is None:  # only x' was used: the plain residual backward
+            if dxp is None:
+                return None, None, None, None, None, None
+            dxp = dxp.contiguous()
+            if ctx.p == 0.0:
+                return dxp, dxp, None, None, None, None
+            dh = hip_ops().residual_dropout_bwd(dxp, ctx.p, ctx.seed)
+            return dxp, dh, None, None, None, None
+        g, dh, dw = hip_ops().residual_ln_bwd(
+            dy.contiguous(), xp, w.contiguous(), rstd, mean,
+            None if dxp is None else dxp.contiguous(), ctx.p, ctx.seed,
+        )
+        return g, dh, dw, None, None, None
+
+
+def residual_dropout_add_ln(
+    x: torch.Tensor, h: torch.Tensor, p: float, training: bool,
+    w: torch.Tensor, eps: float = 1e-6,
+):
+    """(x', y) with x' = x + dropout(h, p) and y = LayerNorm(x') * w.
+
+    GPU bf16 with C % 8 == 0 and 64 <= C/8 <= 1024: one kernel each way
+    (ops/csrc/layernorm.hip), same bits and same dropout-seed draw as
+    residual_dropout_add followed by layer_norm. Everything else composes
+    those two ops."""
+    C = x.shape[-1]
+    if (
+        x.is_cuda
+        and x.dtype == torch.bfloat16
+        and h.dtype == torch.bfloat16
+        and w.dtype == torch.bfloat16
+        and h.shape == x.shape
+        and C % 8 == 0
+        and 64 <= C // 8 <= 1024
+    ):
+        return _ResidualDropoutLnFn.apply(x, h, w, p, training, eps)
+    xp = residual_dropout_add(x, h, p, training)
+    return xp, layer_norm(xp, w, eps)
+
+
+# ---------------------------------------------------------------------------
 # Fused cross entropy (gather-based, never one-hot)
 # ---------------------------------------------------------------------------
 
@@ -613,6 +697,7 @@ def adamw_step(
     weight_decay: float = 0.0,
     clip_value: float = 1.0,
     grad_scale: float = 1.0,
+    sumsq_out: Optional[torch.Tensor] = None,
 ) -> None:
     """One fused AdamW step on a flat shard; optionally emits bf16 params.
 
@@ -623,6 +708,11 @@ def adamw_step(
     (0 for no-decay buckets), -lr scale. When `param_bf16_out` is given the
     updated fp32 params are also written as bf16 (the working copy that gets
     all-gathered).
+
+    `sumsq_out`: optional 1-element fp32 tensor that receives the sum of
+    squares of `grad` as stored (before grad_scale and the clip). On GPU it
+    comes out of the update kernel's own pass over the gradient, reduced in
+    a fixed order (no atomics): the same bits on every call.
     """
     if param_f32.is_cuda:
         hip_ops().adamw_step(
@@ -639,8 +729,11 @@ def adamw_step(
             float(weight_decay),
             float(clip_value),
             float(grad_scale),
+            sumsq_out,
         )
     else:
+        if sumsq_out is not None:
+            sumsq_out.copy_(reference.grad_sumsq(grad).reshape(sumsq_out.shape))
         reference.adamw_update(
             param_f32, grad, exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps,
             weight_decay, clip_value, grad_scale,

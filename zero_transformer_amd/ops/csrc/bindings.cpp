@@ -17,7 +17,14 @@ at::Tensor cross_entropy_bwd(at::Tensor logits, at::Tensor targets, at::Tensor l
                              at::Tensor dloss, int64_t divisor);
 void adamw_step(at::Tensor p, at::Tensor p_bf16, at::Tensor g, at::Tensor m,
                 at::Tensor v, long step, double lr, double beta1, double beta2,
-                double eps, double wd, double clip, double grad_scale);
+                double eps, double wd, double clip, double grad_scale,
+                c10::optional<at::Tensor> sumsq_out);
+std::vector<at::Tensor> residual_ln_fwd(at::Tensor x, at::Tensor h, at::Tensor w,
+                                        double p, int64_t seed, double eps);
+std::vector<at::Tensor> residual_ln_bwd(at::Tensor dy, at::Tensor xp, at::Tensor w,
+                                        at::Tensor rstd, at::Tensor mean,
+                                        c10::optional<at::Tensor> dxp, double p,
+                                        int64_t seed);
 at::Tensor residual_dropout_fwd(at::Tensor x, at::Tensor h, double p, int64_t seed);
 at::Tensor residual_dropout_bwd(at::Tensor dy, double p, int64_t seed);
 at::Tensor attn_decode(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor slopes,
@@ -55,7 +62,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gelu_bwd", &gelu_bwd, "tanh GELU bwd (gfx950)");
   m.def("cross_entropy_fwd", &cross_entropy_fwd, "fused gather CE fwd (gfx950)");
   m.def("cross_entropy_bwd", &cross_entropy_bwd, "fused gather CE bwd (gfx950)");
-  m.def("adamw_step", &adamw_step, "fused ZeRO-1 AdamW shard step (gfx950)");
+  m.def("adamw_step", &adamw_step,
+        "fused ZeRO-1 AdamW shard step, optionally returning sum(g^2) (gfx950)",
+        pybind11::arg("p"), pybind11::arg("p_bf16"), pybind11::arg("g"),
+        pybind11::arg("m"), pybind11::arg("v"), pybind11::arg("step"),
+        pybind11::arg("lr"), pybind11::arg("beta1"), pybind11::arg("beta2"),
+        pybind11::arg("eps"), pybind11::arg("wd"), pybind11::arg("clip"),
+        pybind11::arg("grad_scale"), pybind11::arg("sumsq_out") = pybind11::none());
+  m.def("residual_ln_fwd", &residual_ln_fwd,
+        "fused x + dropout(h) and LayerNorm of it, fwd (gfx950)");
+  m.def("residual_ln_bwd", &residual_ln_bwd,
+        "fused LayerNorm bwd + residual grad sum + dropout bwd (gfx950)");
   m.def("residual_dropout_fwd", &residual_dropout_fwd, "fused x + dropout(h) fwd (gfx950)");
   m.def("residual_dropout_bwd", &residual_dropout_bwd, "fused x + dropout(h) bwd (gfx950)");
   m.def("attn_decode", &attn_decode, "single-token KV-cache ALiBi attention (gfx950)");

@@ -142,6 +142,14 @@ ZTA_DEV uint32_t drop_bits32(uint32_t seed, int bhT_qi, int kgroup) {
                ((uint32_t)kgroup * 0x85ebca6bu));
 }
 
+// Residual-dropout mask word for 4 consecutive elements of a flat tensor
+// (residual.hip and the fused residual + LayerNorm kernels of layernorm.hip):
+// element i keeps iff byte (i & 3) of rd_bits(seed, i >> 2) >= thr.
+ZTA_DEV uint32_t rd_bits(uint32_t seed, long i4) {
+  // i4 = element_index / 4; split so the 32-bit hash inputs stay distinct
+  return drop_bits32(seed, (int)(i4 >> 16), (int)(i4 & 0xffff));
+}
+
 // ---------------------------------------------------------------------------
 // Grid sizing helper (G11): cap memory-bound grids, grid-stride the rest.
 // ---------------------------------------------------------------------------

@@ -297,6 +297,181 @@ __global__ __launch_bounds__(1024) void add_ln_vec(
   }
 }
 
+// ---------------------------------------------------------------------------
+// Fused residual-add + dropout + LayerNorm for TRAINING (bf16 vector path):
+//   x' = x + dropout(h, p);  y = LN(x') * w
+// res_drop_fwd followed by ln_fwd_vec is 5 passes over one activation
+// (read x, h, write x'; read x', write y); here 4. The mask is the one of
+// residual.hip (rd_bits on the flat element index; a thread's 8 elements
+// start at a multiple of 8). x' is rounded to bf16 before the statistics,
+// and the statistics and y repeat ln_fwd_vec's arithmetic on the rounded
+// value, so x', y, mean, rstd carry the bits of the two-kernel chain.
+// DROP = false (p == 0 / eval): no hash, x' = bf16(x + h).
+// ---------------------------------------------------------------------------
+template <bool PARTIAL, bool DROP>
+__global__ __launch_bounds__(1024) void res_ln_fwd_vec(
+    const uint16_t* __restrict__ x, const uint16_t* __restrict__ h,
+    const uint16_t* __restrict__ w, uint16_t* __restrict__ xp,
+    uint16_t* __restrict__ y, float* __restrict__ mean_out,
+    float* __restrict__ rstd_out, long rows, int C, float eps, uint32_t thr,
+    float inv_keep, uint32_t seed) {
+  __shared__ float scratch[16];
+  const int t = threadIdx.x;
+  const bool live = !PARTIAL || t * 8 < C;
+  float wv[8];
+  {
+    s16x8 w8 = {};
+    if (live) w8 = *reinterpret_cast<const s16x8*>(&w[t * 8]);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) wv[e] = bf16_to_f32((uint16_t)w8[e]);
+  }
+  const float invC = 1.0f / (float)C;
+  for (long row = blockIdx.x; row < rows; row += gridDim.x) {
+    const long i = row * C + t * 8;
+    s16x8 x8 = {}, h8 = {};
+    if (live) {
+      x8 = *reinterpret_cast<const s16x8*>(&x[i]);
+      h8 = *reinterpret_cast<const s16x8*>(&h[i]);
+    }
+    uint32_t b0 = 0, b1 = 0;
+    if (DROP) {
+      b0 = rd_bits(seed, i >> 2);
+      b1 = rd_bits(seed, (i >> 2) + 1);
+    }
+    s16x8 p8;
+    float xv[8];
+    float sum = 0.f, sumsq = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float hv = bf16_to_f32((uint16_t)h8[e]);
+      if (DROP) {
+        const uint32_t bits = e < 4 ? b0 : b1;
+        const bool keep = ((bits >> (8 * (e & 3))) & 0xffu) >= thr;
+        hv = keep ? hv * inv_keep : 0.f;
+      }
+      const uint16_t r = f32_to_bf16(bf16_to_f32((uint16_t)x8[e]) + hv);
+      p8[e] = (short)r;
+      xv[e] = bf16_to_f32(r);
+      sum += xv[e];
+      sumsq += xv[e] * xv[e];
+    }
+    if (live) *reinterpret_cast<s16x8*>(&xp[i]) = p8;
+    sum = block_reduce_sum(sum, scratch);
+    sumsq = block_reduce_sum(sumsq, scratch);
+    const float mu = sum * invC;
+    const float rstd = rsqrtf(sumsq * invC - mu * mu + eps);
+    if (t == 0) {
+      mean_out[row] = mu;
+      rstd_out[row] = rstd;
+    }
+    s16x8 y8;
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      y8[e] = (short)f32_to_bf16((xv[e] - mu) * rstd * wv[e]);
+    if (live) *reinterpret_cast<s16x8*>(&y[i]) = y8;
+  }
+}
+
+// Backward of the above, and of the residual add that consumed x':
+//   g  = bf16(d(x') + bf16(LN-dx))   gradient of x (and of x' upstream)
+//   dh = mask(g) * inv_keep          as res_drop_bwd
+// ln_bwd_vec + torch add + res_drop_bwd is 8 passes (3 + 3 + 2); here 5
+// (read dy, x', d(x'); write g, dh). Rounds where the chain rounds (LN-dx,
+// the sum, dh from the rounded sum), so g and dh carry its bits; dw_part
+// has ln_bwd_vec's layout and goes through ln_dw_reduce. HAS_DXP = false:
+// nothing arrives down the residual stream (final norm), g = bf16(LN-dx).
+// DROP = false: dh is g, nothing further is written.
+template <bool PARTIAL, bool HAS_DXP, bool DROP>
+__global__ __launch_bounds__(1024) void res_ln_bwd_vec(
+    const uint16_t* __restrict__ dy, const uint16_t* __restrict__ xp,
+    const uint16_t* __restrict__ w, const float* __restrict__ mean,
+    const float* __restrict__ rstd, const uint16_t* __restrict__ dxp,
+    uint16_t* __restrict__ g_out, uint16_t* __restrict__ dh,
+    float* __restrict__ dw_part, long rows, int C, uint32_t thr, float inv_keep,
+    uint32_t seed) {
+  __shared__ float scratch[32];
+  const int t = threadIdx.x;
+  const bool live = !PARTIAL || t * 8 < C;
+  float wv[8], dw_acc[8];
+  {
+    s16x8 w8 = {};
+    if (live) w8 = *reinterpret_cast<const s16x8*>(&w[t * 8]);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      wv[e] = bf16_to_f32((uint16_t)w8[e]);
+      dw_acc[e] = 0.f;
+    }
+  }
+  const float invC = 1.0f / (float)C;
+  const int lane = t & (WAVE - 1), wid = t / WAVE, nw = blockDim.x / WAVE;
+  for (long row = blockIdx.x; row < rows; row += gridDim.x) {
+    const long i = row * C + t * 8;
+    s16x8 dy8 = {}, x8 = {}, r8 = {};
+    if (live) {
+      dy8 = *reinterpret_cast<const s16x8*>(&dy[i]);
+      x8 = *reinterpret_cast<const s16x8*>(&xp[i]);
+      if (HAS_DXP) r8 = *reinterpret_cast<const s16x8*>(&dxp[i]);
+    }
+    const float mu = mean[row], rs = rstd[row];
+    float g[8], xh[8];
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float d = bf16_to_f32((uint16_t)dy8[e]);
+      xh[e] = (bf16_to_f32((uint16_t)x8[e]) - mu) * rs;
+      g[e] = d * wv[e];
+      s1 += g[e];
+      s2 += g[e] * xh[e];
+      dw_acc[e] += d * xh[e];
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      s1 += __shfl_xor(s1, off, WAVE);
+      s2 += __shfl_xor(s2, off, WAVE);
+    }
+    if (lane == 0) {
+      scratch[wid] = s1;
+      scratch[16 + wid] = s2;
+    }
+    __syncthreads();
+    s1 = 0.f;
+    s2 = 0.f;
+    for (int k = 0; k < nw; ++k) {
+      s1 += scratch[k];
+      s2 += scratch[16 + k];
+    }
+    __syncthreads();
+    s1 *= invC;
+    s2 *= invC;
+    uint32_t b0 = 0, b1 = 0;
+    if (DROP) {
+      b0 = rd_bits(seed, i >> 2);
+      b1 = rd_bits(seed, (i >> 2) + 1);
+    }
+    s16x8 g8, h8;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      uint16_t r = f32_to_bf16((g[e] - s1 - xh[e] * s2) * rs);
+      if (HAS_DXP) r = f32_to_bf16(bf16_to_f32((uint16_t)r8[e]) + bf16_to_f32(r));
+      g8[e] = (short)r;
+      if (DROP) {
+        const uint32_t bits = e < 4 ? b0 : b1;
+        const bool keep = ((bits >> (8 * (e & 3))) & 0xffu) >= thr;
+        h8[e] = keep ? (short)f32_to_bf16(bf16_to_f32(r) * inv_keep) : (short)0;
+      }
+    }
+    if (live) {
+      *reinterpret_cast<s16x8*>(&g_out[i]) = g8;
+      if (DROP) *reinterpret_cast<s16x8*>(&dh[i]) = h8;
+    }
+  }
+  if (!live) return;
+  f32x4 p0 = {dw_acc[0], dw_acc[1], dw_acc[2], dw_acc[3]};
+  f32x4 p1 = {dw_acc[4], dw_acc[5], dw_acc[6], dw_acc[7]};
+  *reinterpret_cast<f32x4*>(&dw_part[(long)blockIdx.x * C + t * 8]) = p0;
+  *reinterpret_cast<f32x4*>(&dw_part[(long)blockIdx.x * C + t * 8 + 4]) = p1;
+}
+
 // Vector-path block: one thread per 8 columns, rounded up to whole waves.
 inline int vec_block(int C) { return (C / 8 + WAVE - 1) / WAVE * WAVE; }
 
@@ -430,4 +605,118 @@ std::vector<at::Tensor> layernorm_bwd(at::Tensor dy, at::Tensor x, at::Tensor w,
     }
   }
   return {dx, dw_f32.to(x.scalar_type())};
+}
+
+namespace {
+
+// thr / inv_keep of residual.hip
+inline uint32_t drop_thr(double p) { return (uint32_t)(p * 256.0 + 0.5); }
+inline float drop_inv_keep(uint32_t thr) {
+  return thr ? 256.0f / (256.0f - (float)thr) : 1.0f;
+}
+
+void check_res_ln(const at::Tensor& a, const at::Tensor& w, const char* what) {
+  TORCH_CHECK(a.is_cuda() && a.is_contiguous() && w.is_contiguous() && w.dim() == 1,
+              what, ": contiguous device tensors");
+  TORCH_CHECK(a.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16,
+              what, ": bf16 only");
+  const long C = a.size(-1);
+  TORCH_CHECK(C % 8 == 0 && C / 8 >= 64 && C / 8 <= 1024 && w.numel() == C, what,
+              ": C/8 must be in [64, 1024]");
+}
+
+}  // namespace
+
+// x' = x + dropout(h, p), y = LayerNorm(x') * w  ->  {x', y, rstd, mean}
+std::vector<at::Tensor> residual_ln_fwd(at::Tensor x, at::Tensor h, at::Tensor w,
+                                        double p, int64_t seed, double eps) {
+  check_res_ln(x, w, "residual_ln_fwd");
+  TORCH_CHECK(h.is_cuda() && h.is_contiguous() && h.scalar_type() == at::kBFloat16 &&
+              h.sizes() == x.sizes());
+  const int C = x.size(-1);
+  const long rows = x.numel() / C;
+  auto xp = at::empty_like(x);
+  auto y = at::empty_like(x);
+  auto mean = at::empty({rows}, x.options().dtype(at::kFloat));
+  auto rstd = at::empty({rows}, x.options().dtype(at::kFloat));
+  if (rows == 0) return {xp, y, rstd, mean};
+  const uint32_t thr = drop_thr(p);
+  const float inv_keep = drop_inv_keep(thr);
+  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
+  const int block = vec_block(C);
+  const int grid = int(std::min<long>(rows, 4096));
+#define ZTA_RES_LN_FWD(PARTIALV, DROPV)                                              \
+  hipLaunchKernelGGL((res_ln_fwd_vec<PARTIALV, DROPV>), dim3(grid), dim3(block), 0,  \
+                     stream, (const uint16_t*)x.data_ptr(),                          \
+                     (const uint16_t*)h.data_ptr(), (const uint16_t*)w.data_ptr(),   \
+                     (uint16_t*)xp.data_ptr(), (uint16_t*)y.data_ptr(),              \
+                     mean.data_ptr<float>(), rstd.data_ptr<float>(), rows, C,        \
+                     (float)eps, thr, inv_keep, (uint32_t)seed)
+  const bool partial = block * 8 != C;
+  if (thr) {
+    if (partial) ZTA_RES_LN_FWD(true, true);
+    else ZTA_RES_LN_FWD(false, true);
+  } else {
+    if (partial) ZTA_RES_LN_FWD(true, false);
+    else ZTA_RES_LN_FWD(false, false);
+  }
+#undef ZTA_RES_LN_FWD
+  return {xp, y, rstd, mean};
+}
+
+// -> {g, dh, dw}: g = d(x') + LN-dx (the gradient of x), dh = dropout-masked
+// g (the same tensor as g when p == 0), dw of the LayerNorm weight. `dxp` is
+// the gradient arriving at x' from further down the residual stream, absent
+// when x' fed nothing but the LayerNorm.
+std::vector<at::Tensor> residual_ln_bwd(at::Tensor dy, at::Tensor xp, at::Tensor w,
+                                        at::Tensor rstd, at::Tensor mean,
+                                        c10::optional<at::Tensor> dxp, double p,
+                                        int64_t seed) {
+  check_res_ln(xp, w, "residual_ln_bwd");
+  TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() && dy.scalar_type() == at::kBFloat16 &&
+              dy.sizes() == xp.sizes());
+  const int C = xp.size(-1);
+  const long rows = xp.numel() / C;
+  TORCH_CHECK(rstd.scalar_type() == at::kFloat && mean.scalar_type() == at::kFloat &&
+              rstd.numel() == rows && mean.numel() == rows);
+  const bool has = dxp.has_value() && dxp->defined();
+  if (has)
+    TORCH_CHECK(dxp->is_cuda() && dxp->is_contiguous() &&
+                dxp->scalar_type() == at::kBFloat16 && dxp->sizes() == xp.sizes());
+  const uint32_t thr = drop_thr(p);
+  const float inv_keep = drop_inv_keep(thr);
+  auto g = at::empty_like(xp);
+  auto dh = thr ? at::empty_like(xp) : g;
+  auto dw_f32 = at::zeros({C}, xp.options().dtype(at::kFloat));
+  if (rows == 0) return {g, dh, dw_f32.to(xp.scalar_type())};
+  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA();
+  const int block = vec_block(C);
+  const int grid = int(std::min<long>(rows, 4096));  // as layernorm_bwd
+  auto dw_part = at::empty({grid, C}, xp.options().dtype(at::kFloat));
+  const uint16_t* dxp_ptr = has ? (const uint16_t*)dxp->data_ptr() : nullptr;
+#define ZTA_RES_LN_BWD(PARTIALV, HASV, DROPV)                                         \
+  hipLaunchKernelGGL((res_ln_bwd_vec<PARTIALV, HASV, DROPV>), dim3(grid),             \
+                     dim3(block), 0, stream, (const uint16_t*)dy.data_ptr(),          \
+                     (const uint16_t*)xp.data_ptr(), (const uint16_t*)w.data_ptr(),   \
+                     mean.data_ptr<float>(), rstd.data_ptr<float>(), dxp_ptr,         \
+                     (uint16_t*)g.data_ptr(), (uint16_t*)dh.data_ptr(),               \
+                     dw_part.data_ptr<float>(), rows, C, thr, inv_keep,               \
+                     (uint32_t)seed)
+#define ZTA_RES_LN_BWD_P(HASV, DROPV)               \
+  do {                                              \
+    if (block * 8 != C) ZTA_RES_LN_BWD(true, HASV, DROPV); \
+    else ZTA_RES_LN_BWD(false, HASV, DROPV);        \
+  } while (0)
+  if (has) {
+    if (thr) ZTA_RES_LN_BWD_P(true, true);
+    else ZTA_RES_LN_BWD_P(true, false);
+  } else {
+    if (thr) ZTA_RES_LN_BWD_P(false, true);
+    else ZTA_RES_LN_BWD_P(false, false);
+  }
+#undef ZTA_RES_LN_BWD_P
+#undef ZTA_RES_LN_BWD
+  hipLaunchKernelGGL(ln_dw_reduce, dim3((C + 255) / 256, 64), dim3(256), 0, stream,
+                     dw_part.data_ptr<float>(), dw_f32.data_ptr<float>(), C, grid);
+  return {g, dh, dw_f32.to(xp.scalar_type())};
 }

@@ -20,11 +20,6 @@
 
 namespace {
 
-ZTA_DEV uint32_t rd_bits(uint32_t seed, long i4) {
-  // i4 = element_index / 4; split so the 32-bit hash inputs stay distinct
-  return drop_bits32(seed, (int)(i4 >> 16), (int)(i4 & 0xffff));
-}
-
 __global__ __launch_bounds__(256) void res_drop_fwd(
     const uint16_t* __restrict__ x, const uint16_t* __restrict__ h,
     uint16_t* __restrict__ y, long n, uint32_t thr, float inv_keep,

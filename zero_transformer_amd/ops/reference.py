@@ -441,6 +441,12 @@ def cross_entropy(logits: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
     return F.cross_entropy(logits.float(), targets, ignore_index=-1)
 
 
+def grad_sumsq(grad: torch.Tensor) -> torch.Tensor:
+    """fp32 sum of squares of a gradient shard as stored (the grad-norm
+    metric's per-shard term; the GPU AdamW kernel returns the same sum)."""
+    return grad.float().square().sum()
+
+
 def adamw_update(
     param_f32: torch.Tensor,
     grad: torch.Tensor,

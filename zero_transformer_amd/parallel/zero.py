@@ -141,7 +141,12 @@ class ZeRO1Optimizer:
         shard_n = numel // self.world
         b.flat_param = torch.zeros(numel, dtype=wd, device=dev)
         b.flat_grad = torch.zeros(numel, dtype=wd, device=dev)
-        b.grad_shard = torch.zeros(shard_n, dtype=wd, device=dev)
+        # one rank: the shard is the whole bucket, so it is the same storage
+        # (reduce-scatter would be a copy of flat_grad onto itself)
+        b.grad_shard = (
+            b.flat_grad if self.world == 1
+            else torch.zeros(shard_n, dtype=wd, device=dev)
+        )
         # fp32 master shard initialized from the (possibly fp32) params
         master_full = torch.zeros(numel, dtype=torch.float32, device=dev)
         for p, o in zip(params, offsets):
@@ -156,12 +161,17 @@ class ZeRO1Optimizer:
     def _install_views_and_hooks(self):
         self._grad_view: Dict[int, torch.Tensor] = {}
         self._accumulated: set = set()
+        self._counted: set = set()  # parameters counted into b.ready this step
         for b in self.buckets:
             for p, o in zip(b.params, b.offsets):
                 shape = p.data.shape
                 p.data = b.flat_param[o : o + p.numel()].view(shape)
                 self._grad_view[id(p)] = b.flat_grad[o : o + p.numel()].view(shape)
                 p.register_post_accumulate_grad_hook(self._on_grad_ready)
+                # ops.linear's backward asks here for the bucket view so its
+                # weight-gradient GEMM can write the first gradient of a step
+                # in place (first_grad_view / grad_written)
+                p._zta_grad_sink = self
 
     # ------------------------------------------------------------------
     def set_sync(self, sync: bool):
@@ -181,20 +191,58 @@ class ZeRO1Optimizer:
         # accumulation and removed — see profiles/PERF.md before rebuilding.
         view = self._grad_view[id(p)]
         g = p.grad
+        if g is None:
+            # the producer wrote the bucket view itself and returned no
+            # gradient (first_grad_view / grad_written counted it already).
+            # Reached in practice: the hook also runs after a backward that
+            # handed autograd None for p (without this return the add_ below
+            # raised on None in the end-to-end smoke run).
+            return
         if g is not view:
             first = id(p) not in self._accumulated
             if first:
                 self._accumulated.add(id(p))
             view.copy_(g) if first else view.add_(g)
             p.grad = None
+        self._count_ready(p)
+
+    def first_grad_view(self, p: torch.nn.Parameter) -> Optional[torch.Tensor]:
+        """p's view of the flat gradient bucket if p has no gradient yet in
+        this step (a producer may then write the gradient straight into it
+        and call grad_written), else None: later gradients take the
+        temporary + add_ path of _on_grad_ready.
+
+        Limits of this protocol (ops._LinearFn.backward is its one user): a
+        parameter may reach ops.linear once per backward. A second use in
+        the same backward is still added correctly, but the bucket counts
+        the parameter at its first gradient, so with several ranks the
+        reduce could start before the second one is added. And the producer
+        returns None for the weight: torch.autograd.grad() on a model whose
+        optimizer is attached gets None there (the gradient is in the
+        bucket), and create_graph=True is not supported."""
+        return None if id(p) in self._accumulated else self._grad_view[id(p)]
+
+    def grad_written(self, p: torch.nn.Parameter):
+        """The first gradient of the step now stands in first_grad_view(p):
+        the bookkeeping of _on_grad_ready without the copy. The writer ran on
+        the current stream, like the copy it replaces."""
+        self._accumulated.add(id(p))
+        self._count_ready(p)
+
+    def _count_ready(self, p: torch.nn.Parameter):
         if not self._sync:
             return
+        if id(p) in self._counted:  # once per parameter and step
+            return
+        self._counted.add(id(p))
         b, _ = self._param_bucket[id(p)]
         b.ready += 1
         if b.ready == len(b.params):
             self._launch_reduce(b)
 
     def _launch_reduce(self, b: Bucket):
+        if b.grad_shard is b.flat_grad:  # one rank: nothing to reduce or move
+            return
         if self.overlap_comm:
             self._comm_stream.wait_stream(torch.cuda.current_stream(self.device))
             with torch.cuda.stream(self._comm_stream):
@@ -223,13 +271,17 @@ class ZeRO1Optimizer:
         # shards partition the param set, so all-reduce(SUM) of per-shard
         # sum-of-squares is the full-tree sum. grad_shard holds the
         # rank-averaged micro-step SUM; / accum gives the true mean grad.
-        sq = torch.zeros((), dtype=torch.float32, device=self.device)
-        for b in self.buckets:
-            sq += b.grad_shard.float().square().sum()
-        if self.world > 1:
-            comm.all_reduce_sum_(sq)
-        self.last_grad_norm = sq.sqrt() / self.accum_steps  # 0-d tensor
-        for b in self.buckets:
+        # On GPU the AdamW kernel returns each bucket's sum of squares from
+        # its own read of the gradient (fixed-order reduction, no atomics);
+        # the CPU path sums here.
+        on_gpu = self.device.type == "cuda"
+        if on_gpu:
+            sq_parts = torch.empty(len(self.buckets), dtype=torch.float32, device=self.device)
+        else:
+            sq = torch.zeros((), dtype=torch.float32, device=self.device)
+            for b in self.buckets:
+                sq += ops.reference.grad_sumsq(b.grad_shard)
+        for i, b in enumerate(self.buckets):
             shard_n = b.numel // self.world
             own = b.flat_param[self.rank * shard_n : (self.rank + 1) * shard_n]
             ops.adamw_step(
@@ -246,6 +298,7 @@ class ZeRO1Optimizer:
                 self.weight_decay if b.decay else 0.0,
                 self.clip_value,
                 grad_scale=1.0 / self.accum_steps,
+                sumsq_out=sq_parts[i : i + 1] if on_gpu else None,
             )
             if self.param_dtype != torch.bfloat16:
                 own.copy_(b.master.to(self.param_dtype))
@@ -261,6 +314,11 @@ class ZeRO1Optimizer:
             # world == 1: `own` aliases the full flat_param — nothing to gather
         if self.overlap_comm:
             torch.cuda.current_stream(self.device).wait_stream(self._comm_stream)
+        if on_gpu:
+            sq = sq_parts.sum()
+        if self.world > 1:
+            comm.all_reduce_sum_(sq)
+        self.last_grad_norm = sq.sqrt() / self.accum_steps  # 0-d tensor
         self.zero_grad()
         return lr
 
@@ -273,6 +331,7 @@ class ZeRO1Optimizer:
         # regions are zeroed lazily in step() for params whose hook never
         # fired.
         self._accumulated.clear()
+        self._counted.clear()
         for b in self.buckets:
             for p in b.params:
                 p.grad = None
