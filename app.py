@@ -234,6 +234,9 @@ def main():
                    help="--paged: sequences decoded per step")
     p.add_argument("--kv-pages", type=int, default=256,
                    help="--paged: pages of 64 rows in the KV pool (page 0 is reserved)")
+    p.add_argument("--w8", action="store_true",
+                   help="weight-only int8 block projections (W8A16): half the "
+                        "weight bytes per decode step")
     p.add_argument("--serve", action="store_true")
     p.add_argument("--port", type=int, default=7860)
     p.add_argument(
@@ -246,6 +249,10 @@ def main():
 
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     model = model_creator(args.model_size, args.checkpoint, device)
+    if args.w8:  # int8 rows for the blocks' projection weights (models/quant.py)
+        from zero_transformer_amd.models.quant import quantize_w8_
+
+        quantize_w8_(model)
     tok = load_tokenizer()
     kw = dict(
         max_new_tokens=args.max_new_tokens,

@@ -79,6 +79,8 @@ def main():
                    help="pages in the pool (0: what --batch full-length requests need)")
     p.add_argument("--prefill-chunk", type=int, default=None)
     p.add_argument("--runs", type=int, default=15)
+    p.add_argument("--w8", action="store_true",
+                   help="quantize the block projections to int8 rows after load")
     args = p.parse_args()
     if args.sampler:
         return bench_sampler(args)
@@ -91,6 +93,10 @@ def main():
     torch.manual_seed(0)
     model = model_getter(args.model_size).to(dev)
     model = (model.half() if args.dtype == "fp16" else model.to(torch.bfloat16)).eval()
+    if args.w8:
+        from zero_transformer_amd.models.quant import quantize_w8_
+
+        quantize_w8_(model)
 
     idx = torch.randint(0, model.vocab_size, (args.batch, args.prompt_len), device=dev)
 

@@ -1,6 +1,7 @@
 """Decode-GEMV microbenchmark: GB/s on the weight stream per shape.
 
     python tools/gemv_bench.py [--dtype fp16] [--iters 200]
+    python tools/gemv_bench.py --w8 [--batches 1 2 3 4 8 16] [--rounds 5]
 
 Compares ops/csrc/gemv.hip against torch F.linear (hipBLASLt) on the 1.3B
 decode shapes. The weight stream is the bound (profiles/PERF.md): report
@@ -45,8 +46,48 @@ def bench(fn, iters):
     return (time.perf_counter() - t0) / (iters // 10) / 10
 
 
+W8_SHAPES = [(6144, 2048), (2048, 2048), (8192, 2048), (2048, 8192)]  # 1.3B blocks
+
+
+def bench_w8(args, dt, dev):
+    """Both bodies of ops/csrc/gemv_w8.hip next to what ops.decode_linear runs
+    for the same shape in 16 bits, the sides alternating over --rounds; the
+    median per side, in us and in weight bytes over time."""
+    from zero_transformer_amd import ops
+    from zero_transformer_amd.ops.reference import quantize_rows_w8
+
+    ext = ops.hip_ops()
+    print(f"W8A16 vs 16-bit decode_linear ({args.dtype}); us | TB/s of weight bytes")
+    for N, K in W8_SHAPES:
+        w = torch.randn(N, K, device=dev, dtype=dt) * 0.02
+        q, scale = quantize_rows_w8(w)
+        for B in args.batches:
+            x = torch.randn(B, K, device=dev, dtype=dt)
+            sides = {"w16": lambda: ops.decode_linear(x, w),
+                     "w8_gemm": lambda: ext.w8_gemm(x, q, scale)}
+            if B <= 4:
+                sides["w8_gemv"] = lambda: ext.w8_gemv(x, q, scale)
+            for ks in (k for k in args.ksplit if k <= K // 512):
+                sides[f"w8_gemm/ks{ks}"] = lambda ks=ks: ext.w8_gemm(x, q, scale, ks)
+            times = {k: [] for k in sides}
+            for _ in range(args.rounds):
+                for k, fn in sides.items():
+                    times[k].append(bench(fn, args.iters))
+            cells = []
+            for k, ts in times.items():
+                t = sorted(ts)[len(ts) // 2]
+                nbytes = N * K * (2 if k == "w16" else 1)
+                cells.append(f"{k} {t*1e6:7.2f} us {nbytes/t/1e12:5.2f}")
+            print(f"N={N:5d} K={K:5d} rows={B:2d}: " + " | ".join(cells), flush=True)
+
+
 def main():
     p = argparse.ArgumentParser()
+    p.add_argument("--w8", action="store_true",
+                   help="time ops/csrc/gemv_w8.hip next to the 16-bit decode paths")
+    p.add_argument("--rounds", type=int, default=5)
+    p.add_argument("--ksplit", type=int, nargs="*", default=[],
+                   help="--w8: also time the MFMA body with these workgroup K splits")
     p.add_argument("--dtype", default="fp16", choices=["fp16", "bf16"])
     p.add_argument("--iters", type=int, default=200)
     p.add_argument("--batches", type=int, nargs="*", default=[1, 8, 16])
@@ -55,6 +96,8 @@ def main():
     dev = torch.device("cuda", 0)
     from zero_transformer_amd import ops
 
+    if args.w8:
+        return bench_w8(args, dt, dev)
     for B in args.batches:
         print(f"--- batch {B} ({args.dtype}) ---")
         for N, K in SHAPES:

@@ -108,7 +108,7 @@ def resources(remarks: str) -> dict:
 def compile_asm(src: str) -> tuple:
     from zero_transformer_amd.ops.build import hipcc_compile_cmd
 
-    cmd = hipcc_compile_cmd() + ["--cuda-device-only", "-S",
+    cmd = hipcc_compile_cmd(src) + ["--cuda-device-only", "-S",
                                  "-Rpass-analysis=kernel-resource-usage", src, "-o", "-"]
     p = subprocess.run(cmd, capture_output=True, text=True)
     if p.returncode:

@@ -20,14 +20,28 @@ import torch.nn.functional as F
 from .. import ops
 from ..ops.reference import alibi_slopes
 from ..utils.config import load_config
+from .quant import W8Weight
 
 
-def _proj(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
-    """Linear that routes single-token decode through the weight-streaming
-    GEMV kernel (ops.decode_linear); prefill/CPU keep F.linear."""
+def _linear(x: torch.Tensor, w, plain=F.linear) -> torch.Tensor:
+    """x @ w^T for a block projection weight: an int8 weight
+    (models/quant.py) goes to ops.linear_w8 whatever the row count, a plain
+    tensor to `plain`."""
+    if isinstance(w, W8Weight):
+        return ops.linear_w8(x, w.q, w.scale)
+    return plain(x, w)
+
+
+def _proj_plain(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     if x.shape[-2] == 1:
         return ops.decode_linear(x, w)
     return F.linear(x, w)
+
+
+def _proj(x: torch.Tensor, w) -> torch.Tensor:
+    """Linear that routes single-token decode through the weight-streaming
+    GEMV kernel (ops.decode_linear); prefill/CPU keep F.linear."""
+    return _linear(x, w, _proj_plain)
 
 
 class StaticKVCache:
@@ -97,6 +111,8 @@ class InferenceAttention(nn.Module):
         self.key = nn.Linear(dim, dim, bias=False)
         self.value = nn.Linear(dim, dim, bias=False)
         self.fc_resid = nn.Linear(dim, dim, bias=False)
+        # quantize_w8_ puts the int8 fused weight here and drops query / key / value
+        self.qkv_w8 = None
         if alibi:
             self.register_buffer("slopes", alibi_slopes(heads), persistent=False)
         else:
@@ -109,6 +125,8 @@ class InferenceAttention(nn.Module):
 
     def _fused_qkv_w(self, dtype) -> torch.Tensor:
         """The (3C, C) q|k|v weight, materialized lazily."""
+        if self.qkv_w8 is not None:
+            return self.qkv_w8
         if getattr(self, "_qkv_w", None) is None or self._qkv_w.dtype != dtype:
             self._qkv_w = torch.cat(
                 [self.query.weight, self.key.weight, self.value.weight], dim=0
@@ -129,7 +147,7 @@ class InferenceAttention(nn.Module):
             # decode: one fused (3C, C) GEMV instead of three launches (the
             # fused weight is materialized lazily; same total weight-stream
             # bytes, 1/3 the kernel launches and a fuller grid)
-            qkv = ops.decode_linear(x, self._fused_qkv_w(x.dtype))
+            qkv = _linear(x, self._fused_qkv_w(x.dtype), ops.decode_linear)
             if static_cache is not None:
                 # the kernel reads q / k / v straight from the projection
                 # row, appends k / v at device position len-1 (len already
@@ -142,9 +160,13 @@ class InferenceAttention(nn.Module):
             k = k.view(B, T, H, D).transpose(1, 2)
             v = v.view(B, T, H, D).transpose(1, 2)
         else:
-            q = _proj(x, self.query.weight).view(B, T, H, D).transpose(1, 2)
-            k = _proj(x, self.key.weight).view(B, T, H, D).transpose(1, 2)
-            v = _proj(x, self.value.weight).view(B, T, H, D).transpose(1, 2)
+            if self.qkv_w8 is not None:  # row slices of the fused int8 weight
+                wq, wk, wv = (self.qkv_w8.rows(i * C, (i + 1) * C) for i in range(3))
+            else:
+                wq, wk, wv = self.query.weight, self.key.weight, self.value.weight
+            q = _proj(x, wq).view(B, T, H, D).transpose(1, 2)
+            k = _proj(x, wk).view(B, T, H, D).transpose(1, 2)
+            v = _proj(x, wv).view(B, T, H, D).transpose(1, 2)
         if static_cache is not None:
             assert isinstance(static_cache, StaticKVCache), \
                 "a paged cache is filled through GPT2.prefill"
@@ -191,10 +213,10 @@ class InferenceAttention(nn.Module):
         kernel: one fused qkv GEMM, ops.attention_prefill_append (fills cache
         rows start[b]..start[b]+lens[b] and attends over the cache; no mask
         tensor, no index_copy_), the output projection."""
-        qkv = F.linear(x, self._fused_qkv_w(x.dtype))
+        qkv = _linear(x, self._fused_qkv_w(x.dtype))
         out = cache.attend_prefill(layer_idx, qkv, self.num_head, self.slopes,
                                    lens, start)
-        return F.linear(out, self.fc_resid.weight)
+        return _linear(out, self.fc_resid.weight)
 
 
 class InferenceMLP(nn.Module):

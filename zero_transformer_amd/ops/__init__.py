@@ -334,6 +334,54 @@ def decode_linear(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     return torch.nn.functional.linear(x, w)
 
 
+# rows <= this go to the streaming body of ops/csrc/gemv_w8.hip, more to its
+# MFMA body. Measured (profiles/PERF.md "W8A16 decode"): the streaming body
+# wins up to 3 rows on all four 1.3B shapes and at 4 rows on three of them.
+W8_GEMV_MAX_ROWS = 4
+
+
+def linear_w8(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """x (..., K) @ (q (N, K) int8 * scale (N,) fp32)^T -> (..., N) in x's
+    dtype: a linear layer whose weight is stored as int8 rows with one fp32
+    scale per output row (reference.quantize_rows_w8). Inference only (no
+    autograd).
+
+    GPU, bf16 / fp16, K % 512 == 0, 1..16 rows, grad disabled: the kernels
+    of ops/csrc/gemv_w8.hip, which read the int8 weights directly (fp32
+    accumulation, scale applied once to the sum, one rounding). GPU with
+    more rows (prefill) or another K: scale[n] = f[n] * 2^e[n] with f in
+    [1, 2); the dequant kernel of the same file writes q * 2^e (exact in
+    bf16 / fp16) into a temporary, F.linear multiplies, and the columns get
+    the factor f in fp32. The GEMM's 16-bit output is y / f, no larger than
+    y itself, so it overflows only where the 16-bit model would; two
+    roundings, inside the one-ulp parity bound, where a temporary of rounded
+    q * scale is 3x (fp16) to 25x (bf16) outside it. CPU: fp32 reference."""
+    if not x.is_cuda:
+        w = q.float() * scale.float()[:, None]
+        return torch.nn.functional.linear(x.float(), w).to(x.dtype)
+    ext = hip_ops()
+    N, K = q.shape
+    rows = x.numel() // K
+    if (
+        x.dtype in (torch.bfloat16, torch.float16)
+        and K % 512 == 0
+        and 1 <= rows <= 16
+        and not torch.is_grad_enabled()
+    ):
+        x2 = x.reshape(rows, K).contiguous()
+        y = ext.w8_gemv(x2, q, scale) if rows <= W8_GEMV_MAX_ROWS else ext.w8_gemm(x2, q, scale)
+        return y.view(*x.shape[:-1], N)
+    if x.dtype in (torch.bfloat16, torch.float16) and K % 16 == 0:
+        # 2^e clamped so that q * 2^e is a normal number of the type (|q| >= 1
+        # needs 2^-14 in fp16); a smaller scale leaves f < 1. scale 0: f = 0.
+        mant, exp = torch.frexp(scale)
+        exp = (exp - 1).clamp(min=-14 if x.dtype == torch.float16 else -120)
+        pow2 = torch.ldexp(torch.ones_like(scale), exp)
+        w = ext.dequant_w8(q, pow2, x.dtype == torch.bfloat16)
+        return (torch.nn.functional.linear(x, w).float() * (scale / pow2)).to(x.dtype)
+    return torch.nn.functional.linear(x, reference.dequantize_rows_w8(q, scale, x.dtype))
+
+
 def attention_decode(
     q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     slopes: Optional[torch.Tensor],

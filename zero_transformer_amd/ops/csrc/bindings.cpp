@@ -48,6 +48,9 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor qkv, at::Tensor slo
                                  double p_drop, int64_t seed, int64_t fused);
 at::Tensor gemm_gelu(at::Tensor x, at::Tensor w);
 at::Tensor gemv(at::Tensor x, at::Tensor w);
+at::Tensor w8_gemv(at::Tensor x, at::Tensor q, at::Tensor scale);
+at::Tensor w8_gemm(at::Tensor x, at::Tensor q, at::Tensor scale, int64_t ksplit);
+at::Tensor dequant_w8(at::Tensor q, at::Tensor scale, bool bf16);
 std::vector<at::Tensor> sample_rows(at::Tensor logits, c10::optional<at::Tensor> seen,
                                     at::Tensor temperature, at::Tensor top_k,
                                     at::Tensor top_p, at::Tensor penalty,
@@ -99,6 +102,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_gelu", &gemm_gelu,
         "hipBLASLt x@w^T with fused GELU epilogue (no-grad path)");
   m.def("gemv", &gemv, "weight-streaming decode GEMV x@w^T (gfx950)");
+  m.def("w8_gemv", &w8_gemv,
+        "W8A16 streaming GEMV x@(q*scale)^T, B <= 4 (gfx950)");
+  // ksplit: 0 = workgroup K split picked from (N, K)
+  m.def("w8_gemm", &w8_gemm, "W8A16 skinny MFMA GEMM x@(q*scale)^T, B <= 16 (gfx950)",
+        py::arg("x"), py::arg("q"), py::arg("scale"), py::arg("ksplit") = 0);
+  m.def("dequant_w8", &dequant_w8, "int8 rows * fp32 scale -> bf16 (bf16 = true) or fp16 (gfx950)",
+        py::arg("q"), py::arg("scale"), py::arg("bf16"));
   m.def("sample_rows", &sample_rows,
         "fused sort-free sampler, one workgroup per row, per-row options and "
         "counter-based RNG -> {tokens, cut} (gfx950)");

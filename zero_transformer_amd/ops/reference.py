@@ -483,3 +483,27 @@ def adamw_update(
     if weight_decay:
         update = update + weight_decay * param_f32
     param_f32.add_(update, alpha=-lr)
+
+
+# ---------------------------------------------------------------------------
+# Weight-only int8 rows ("W8A16", ops/csrc/gemv_w8.hip)
+# ---------------------------------------------------------------------------
+
+
+def quantize_rows_w8(w: torch.Tensor):
+    """(N, K) bf16 / fp16 / fp32 -> (q int8 (N, K), scale fp32 (N,)).
+
+    In fp32: scale[n] = max_k |w[n, k]| / 127 and q = round_half_even(w /
+    scale) clamped to [-127, 127] (-128 is never produced). A zero row gets
+    scale 0 and q 0."""
+    assert w.dim() == 2, "quantize_rows_w8: w must be (N, K)"
+    wf = w.detach().float()
+    scale = wf.abs().amax(dim=1) / 127.0
+    safe = torch.where(scale > 0, scale, torch.ones_like(scale))
+    q = torch.round(wf / safe[:, None]).clamp_(-127, 127).to(torch.int8)
+    return q.contiguous(), scale
+
+
+def dequantize_rows_w8(q: torch.Tensor, scale: torch.Tensor, dtype) -> torch.Tensor:
+    """q * scale as one fp32 product, rounded once to `dtype`."""
+    return (q.float() * scale.float()[:, None]).to(dtype)
