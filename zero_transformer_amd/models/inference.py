@@ -69,7 +69,7 @@ class StaticKVCache:
         the active ones grow). Device adds: correct inside a graph replay."""
         self.len_t += n
 
-    # The attention layers reach a cache through these two calls, so that
+    # The attention layers reach a cache through these three calls, so that
     # another cache kind (models/paged.py) brings its own addressing.
     def attend_decode(self, layer_idx, qkv, num_head, slopes):
         return ops.attention_decode_append(
@@ -77,6 +77,10 @@ class StaticKVCache:
 
     def attend_prefill(self, layer_idx, qkv, num_head, slopes, lens, start):
         return ops.attention_prefill_append(
+            qkv, self.k[layer_idx], self.v[layer_idx], num_head, slopes, lens, start)
+
+    def attend_verify(self, layer_idx, qkv, num_head, slopes, lens, start):
+        return ops.attention_verify_append(
             qkv, self.k[layer_idx], self.v[layer_idx], num_head, slopes, lens, start)
 
     def set_len(self, n):
@@ -217,6 +221,16 @@ class InferenceAttention(nn.Module):
         out = cache.attend_prefill(layer_idx, qkv, self.num_head, self.slopes,
                                    lens, start)
         return _linear(out, self.fc_resid.weight)
+
+    def verify(self, x: torch.Tensor, cache: "StaticKVCache", layer_idx: int,
+               lens: torch.Tensor, start: torch.Tensor) -> torch.Tensor:
+        """prefill() for the few rows of a speculative verify step: the same
+        result from ops.attention_verify_append, which splits the cache over
+        workgroups, and the decode routing of the two projections."""
+        qkv = _proj(x, self._fused_qkv_w(x.dtype))
+        out = cache.attend_verify(layer_idx, qkv, self.num_head, self.slopes,
+                                  lens, start)
+        return _proj(out, self.fc_resid.weight)
 
 
 class InferenceMLP(nn.Module):
@@ -391,6 +405,30 @@ class GPT2(nn.Module):
         return _proj(x, self.lm_head.weight)[:, 0]
 
     @torch.no_grad()
+    def verify(self, idx: torch.Tensor, cache: StaticKVCache, lens: torch.Tensor,
+               start: torch.Tensor) -> torch.Tensor:
+        """The verify pass of speculative decoding: idx (B, T), T <= 16 rows
+        per sequence, of which the first lens[b] are real and sit behind
+        start[b] cached rows (both (B,) int32 on idx's device, read in-kernel:
+        the call replays from a graph). Appends their K/V rows to `cache` (a
+        StaticKVCache or a paged cache) and returns EVERY row's logits,
+        (B, T, V); rows >= lens[b] hold no information. `cache.len_t` is not
+        used. Block boundaries are the fused add + LayerNorm of _decode_step."""
+        x = self.wte(idx)
+        eps = self.blocks[0].ln1.eps
+        ln_x = F.layer_norm(x, x.shape[-1:], weight=self.blocks[0].ln1.weight,
+                            eps=eps)
+        for i, block in enumerate(self.blocks):
+            a = block.attn.verify(ln_x, cache, i, lens, start)
+            x, ln2_x = ops.add_ln(x, a, block.ln2.weight, eps)
+            m = block.mlp(ln2_x)
+            next_w = (
+                self.blocks[i + 1].ln1.weight if i + 1 < self.N else self.norm.weight
+            )
+            x, ln_x = ops.add_ln(x, m, next_w, eps)
+        return _proj(ln_x, self.lm_head.weight)
+
+    @torch.no_grad()
     def generate(
         self,
         idx: torch.Tensor,
@@ -493,6 +531,122 @@ def generate_fast(
         cur.copy_(nxt)
         out_tokens.append(nxt.clone())
     return torch.cat([idx] + out_tokens, dim=1)
+
+
+def prompt_lookup_draft(tokens: List[List[int]], draft_len: int,
+                        ngram: int) -> List[List[int]]:
+    """Per sequence: the up-to-`draft_len` tokens that followed the most
+    recent earlier occurrence of its last `ngram` tokens (then of its last
+    ngram - 1, ... 1); [] if none of them occurred before."""
+    out = []
+    for seq in tokens:
+        prop: List[int] = []
+        for g in range(min(ngram, len(seq) - 1), 0, -1):
+            tail = seq[-g:]
+            for s in range(len(seq) - g - 1, -1, -1):
+                if seq[s:s + g] == tail:
+                    prop = seq[s + g:s + g + draft_len]
+                    break
+            if prop:
+                break
+        out.append(prop)
+    return out
+
+
+@torch.no_grad()
+def generate_speculative(
+    model: "GPT2",
+    idx: torch.Tensor,
+    max_new_tokens: int,
+    draft_len: int = 4,
+    ngram: int = 3,
+    use_graph: bool = True,
+    draft_fn=None,
+):
+    """generate_fast's greedy tokens, several per model pass: each step
+    scores the pending token and up to `draft_len` drafted ones in one
+    GPT2.verify (at most 15) and keeps the longest drafted prefix the model
+    agrees with, plus the model's own next token.
+
+    -> (tokens (B, T0 + new) as generate_fast returns them, steps, accepted):
+    the verify passes run and the drafted tokens kept, over all sequences.
+
+    Drafts come from `draft_fn(tokens_so_far: List[List[int]]) ->
+    List[List[int]]` (prompt and everything emitted, per sequence; longer
+    proposals are cut to draft_len), by default prompt_lookup_draft with
+    `ngram`; a sequence without a proposal carries one row. With the argmax
+    A[b, i] of row i's logits, draft i is kept while it equals A[b, i - 1];
+    then A at the first disagreement (or behind the last draft) is emitted
+    and becomes the next pending token. Sequences accept independently:
+    start[b] advances by what sequence b emitted, rejected rows stay in the
+    cache behind it and the next step overwrites them.
+
+    The first T0 - 1 prompt tokens go through GPT2.prefill; the last one is
+    the first pending token, so every emitted token comes from a verify step
+    and an always-right draft needs ceil(new / (draft_len + 1)) of them. The
+    step has a fixed shape (B, draft_len + 1) and static idx / lens / start
+    buffers, captured in a hipGraph on the GPU; per step the host uploads the
+    three buffers and reads the argmax back, the one synchronisation.
+    """
+    B, T0 = idx.shape
+    K = int(draft_len)
+    T = K + 1
+    assert max_new_tokens >= 1 and 0 <= K < ops.VERIFY_MAX_ROWS
+    dev = idx.device
+    p = next(model.parameters())
+    H = model.blocks[0].attn.num_head
+    D = model.blocks[0].attn.head_dim
+    n_new = max(1, min(max_new_tokens, model.num_ctx - T0))
+    # a step may write draft_len + 1 rows behind the last kept one; at the
+    # context limit `lens` shortens it (and the op clamps)
+    cache_rows = min(model.num_ctx, T0 + n_new + T)
+    cache = StaticKVCache(model.N, B, H, D, cache_rows, dev, p.dtype)
+    if T0 > 1:
+        cache.set_len(T0 - 1)  # a one-token prefill is a decode step
+        model.prefill(idx[:, :T0 - 1], cache)
+
+    idx_buf = torch.zeros(B, T, dtype=torch.long, device=dev)
+    lens_buf = torch.full((B,), T, dtype=torch.int32, device=dev)
+    start_buf = torch.full((B,), T0 - 1, dtype=torch.int32, device=dev)
+
+    def step():
+        return model.verify(idx_buf, cache, lens_buf, start_buf).argmax(-1)  # (B, T)
+
+    graph = None
+    if use_graph and dev.type == "cuda":
+        # warm-up and capture write rows T0 - 1 .. of every sequence, which
+        # the first real step overwrites
+        graph, am_buf = capture_decode_step(step, cache, max(T0 - 1, 0))
+
+    tokens = [list(row) for row in idx.tolist()]
+    start = [T0 - 1] * B
+    steps = accepted = 0
+    while any(len(t) - T0 < n_new for t in tokens):
+        drafts = (draft_fn(tokens) if draft_fn is not None
+                  else prompt_lookup_draft(tokens, K, ngram))
+        rows = []
+        for b in range(B):
+            left = n_new - (len(tokens[b]) - T0)  # one emitted token per row
+            rows.append(([tokens[b][-1]] + [int(t) for t in drafts[b][:K]])[:max(left, 0)])
+        idx_buf.copy_(torch.tensor([r + [0] * (T - len(r)) for r in rows]))
+        lens_buf.copy_(torch.tensor([len(r) for r in rows], dtype=torch.int32))
+        start_buf.copy_(torch.tensor(start, dtype=torch.int32))
+        if graph is not None:
+            graph.replay()
+            am = am_buf.tolist()
+        else:
+            am = step().tolist()
+        steps += 1
+        for b, r in enumerate(rows):
+            if not r:
+                continue
+            a = 0
+            while a + 1 < len(r) and r[a + 1] == am[b][a]:
+                a += 1
+            tokens[b] += r[1:a + 1] + [am[b][a]]
+            start[b] += a + 1
+            accepted += a
+    return torch.tensor(tokens, dtype=idx.dtype, device=dev), steps, accepted
 
 
 @torch.no_grad()

@@ -41,6 +41,11 @@ class _PagedAttend:
             qkv, self.k[layer_idx], self.v[layer_idx], num_head, slopes,
             self.block_table, lens, start)
 
+    def attend_verify(self, layer_idx, qkv, num_head, slopes, lens, start):
+        return ops.attention_verify_paged(
+            qkv, self.k[layer_idx], self.v[layer_idx], num_head, slopes,
+            self.block_table, lens, start)
+
 
 class _SlotView(_PagedAttend):
     """Some slots of a PagedKVCache, for a prefill of just those: the same

@@ -513,6 +513,56 @@ def attention_prefill_paged(
         qkv.contiguous(), k_pool, v_pool, slopes, block_table, lens, start)
 
 
+VERIFY_MAX_ROWS = 16  # one 16-row MFMA operand (ops/csrc/attn_verify.hip)
+
+
+def attention_verify_append(
+    qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+    num_head: int, slopes: Optional[torch.Tensor], lens: torch.Tensor,
+    start: torch.Tensor,
+) -> torch.Tensor:
+    """The verify pass of speculative decoding: attention_prefill_append
+    (which defines it, arguments and clamps included) for a few rows per
+    sequence against a long cache. On GPU (fp16/bf16, head_dim 32/64/96/128,
+    T <= 16) the keys are split over 8 workgroups per (sequence, head), which
+    stream the cache once for all T rows (ops/csrc/attn_verify.hip); anything
+    else goes to attention_prefill_append. Inference only (no autograd)."""
+    if not (
+        qkv.is_cuda
+        and qkv.dtype in (torch.float16, torch.bfloat16)
+        and k_cache.shape[3] in (32, 64, 96, 128)
+        and qkv.shape[1] <= VERIFY_MAX_ROWS
+    ):
+        return attention_prefill_append(
+            qkv, k_cache, v_cache, num_head, slopes, lens, start)
+    assert k_cache.shape[1] == num_head, "k_cache heads != num_head"
+    if slopes is None:
+        slopes = torch.zeros(num_head, dtype=torch.float32, device=qkv.device)
+    return hip_ops().attn_verify_append(
+        qkv.contiguous(), k_cache, v_cache, slopes, lens, start)
+
+
+def attention_verify_paged(
+    qkv: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor,
+    num_head: int, slopes: Optional[torch.Tensor], block_table: torch.Tensor,
+    lens: torch.Tensor, start: torch.Tensor,
+) -> torch.Tensor:
+    """attention_verify_append on a paged KV cache: attention_prefill_paged
+    defines it; same routing as attention_verify_append (R % 64 != 0 raises on
+    the GPU)."""
+    if not (
+        _paged_on_gpu(qkv, k_pool, lambda d: d in (32, 64, 96, 128))
+        and qkv.shape[1] <= VERIFY_MAX_ROWS
+    ):
+        return attention_prefill_paged(
+            qkv, k_pool, v_pool, num_head, slopes, block_table, lens, start)
+    assert k_pool.shape[1] == num_head, "k_pool heads != num_head"
+    if slopes is None:
+        slopes = torch.zeros(num_head, dtype=torch.float32, device=qkv.device)
+    return hip_ops().attn_verify_paged(
+        qkv.contiguous(), k_pool, v_pool, slopes, block_table, lens, start)
+
+
 def attention_decode_paged(
     qkv: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor,
     num_head: int, slopes: Optional[torch.Tensor], block_table: torch.Tensor,

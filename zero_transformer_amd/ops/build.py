@@ -32,6 +32,7 @@ SOURCES = [
     "attn_decode.hip",
     "attn_prefill.hip",
     "attn_paged.hip",
+    "attn_verify.hip",
     "attention_bwd.hip",
     "gemm_lt.hip",
     "gemv.hip",
@@ -50,6 +51,7 @@ SOURCE_FLAGS = {
     # products); with the flag, none. The older files keep the flags they
     # were verified with, so that their code objects do not change.
     "gemv_w8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "attn_verify.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 
