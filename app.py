@@ -237,6 +237,9 @@ def main():
     p.add_argument("--w8", action="store_true",
                    help="weight-only int8 block projections (W8A16): half the "
                         "weight bytes per decode step")
+    p.add_argument("--w4", action="store_true",
+                   help="weight-only int4 block projections (W4A16, one scale per "
+                        "128 inputs): a quarter of the weight bytes per decode step")
     p.add_argument("--serve", action="store_true")
     p.add_argument("--port", type=int, default=7860)
     p.add_argument(
@@ -253,6 +256,10 @@ def main():
         from zero_transformer_amd.models.quant import quantize_w8_
 
         quantize_w8_(model)
+    if args.w4:  # group-scaled 4-bit codes instead
+        from zero_transformer_amd.models.quant import quantize_w4_
+
+        quantize_w4_(model)
     tok = load_tokenizer()
     kw = dict(
         max_new_tokens=args.max_new_tokens,

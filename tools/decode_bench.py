@@ -81,6 +81,8 @@ def main():
     p.add_argument("--runs", type=int, default=15)
     p.add_argument("--w8", action="store_true",
                    help="quantize the block projections to int8 rows after load")
+    p.add_argument("--w4", action="store_true",
+                   help="quantize the block projections to group-scaled int4 after load")
     args = p.parse_args()
     if args.sampler:
         return bench_sampler(args)
@@ -97,8 +99,15 @@ def main():
         from zero_transformer_amd.models.quant import quantize_w8_
 
         quantize_w8_(model)
+    if args.w4:
+        from zero_transformer_amd.models.quant import quantize_w4_
 
-    idx = torch.randint(0, model.vocab_size, (args.batch, args.prompt_len), device=dev)
+        quantize_w4_(model)
+    if args.w8 or args.w4:
+        ts = [t for b in model.blocks for t in list(b.parameters()) + list(b.buffers())]
+        print(f"block weights: {sum(t.numel() * t.element_size() for t in ts) / 2**20:.0f} MiB")
+
+    idx =torch.randint(0, model.vocab_size, (args.batch, args.prompt_len), device=dev)
 
     @torch.no_grad()
     def run():

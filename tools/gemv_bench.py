@@ -2,6 +2,7 @@
 
     python tools/gemv_bench.py [--dtype fp16] [--iters 200]
     python tools/gemv_bench.py --w8 [--batches 1 2 3 4 8 16] [--rounds 5]
+    python tools/gemv_bench.py --w4 [--batches 1 2 3 4 8 16] [--ksplit 2 4]
 
 Compares ops/csrc/gemv.hip against torch F.linear (hipBLASLt) on the 1.3B
 decode shapes. The weight stream is the bound (profiles/PERF.md): report
@@ -81,13 +82,54 @@ def bench_w8(args, dt, dev):
             print(f"N={N:5d} K={K:5d} rows={B:2d}: " + " | ".join(cells), flush=True)
 
 
+def bench_w4(args, dt, dev):
+    """bench_w8 with the bodies of ops/csrc/gemv_w4.hip and the dequant +
+    F.linear route of ops.linear_w4 added: per shape and row count W4, W8
+    and the 16-bit path from the same call, the sides alternating over
+    --rounds; the median per side, in us and in weight bytes over time (W4:
+    packed codes plus scales)."""
+    from zero_transformer_amd import ops
+    from zero_transformer_amd.ops.reference import quantize_rows_w4, quantize_rows_w8
+
+    ext = ops.hip_ops()
+    torch.set_grad_enabled(False)  # linear_w8 routes to its kernels at inference only
+    print(f"W4A16 vs W8A16 vs 16-bit decode_linear ({args.dtype}); us | TB/s of weight bytes")
+    for N, K in W8_SHAPES:
+        w = torch.randn(N, K, device=dev, dtype=dt) * 0.02
+        q, scale = quantize_rows_w8(w)
+        p4, s4 = quantize_rows_w4(w)
+        nbytes = {"w16": N * K * 2, "w8": N * K, "w4": N * K // 2 + N * K // 128 * 4}
+        for B in args.batches:
+            x = torch.randn(B, K, device=dev, dtype=dt)
+            sides = {"w16": lambda: ops.decode_linear(x, w),
+                     "w8": lambda: ops.linear_w8(x, q, scale),
+                     "w4_gemm": lambda: ext.w4_gemm(x, p4, s4),
+                     "w4_dequant+linear": lambda: torch.nn.functional.linear(
+                         x, ext.dequant_w4(p4, s4, dt == torch.bfloat16))}
+            if B <= 4:
+                sides["w4_gemv"] = lambda: ext.w4_gemv(x, p4, s4)
+            for ks in (k for k in args.ksplit if k <= K // 512):
+                sides[f"w4_gemm/ks{ks}"] = lambda ks=ks: ext.w4_gemm(x, p4, s4, ks)
+            times = {k: [] for k in sides}
+            for _ in range(args.rounds):
+                for k, fn in sides.items():
+                    times[k].append(bench(fn, args.iters))
+            cells = []
+            for k, ts in times.items():
+                t = sorted(ts)[len(ts) // 2]
+                cells.append(f"{k} {t*1e6:7.2f} us {nbytes[k.split('_')[0]]/t/1e12:5.2f}")
+            print(f"N={N:5d} K={K:5d} rows={B:2d}: " + " | ".join(cells), flush=True)
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--w8", action="store_true",
                    help="time ops/csrc/gemv_w8.hip next to the 16-bit decode paths")
+    p.add_argument("--w4", action="store_true",
+                   help="time ops/csrc/gemv_w4.hip next to W8 and the 16-bit decode paths")
     p.add_argument("--rounds", type=int, default=5)
     p.add_argument("--ksplit", type=int, nargs="*", default=[],
-                   help="--w8: also time the MFMA body with these workgroup K splits")
+                   help="--w8 / --w4: also time the MFMA body with these workgroup K splits")
     p.add_argument("--dtype", default="fp16", choices=["fp16", "bf16"])
     p.add_argument("--iters", type=int, default=200)
     p.add_argument("--batches", type=int, nargs="*", default=[1, 8, 16])
@@ -96,6 +138,8 @@ def main():
     dev = torch.device("cuda", 0)
     from zero_transformer_amd import ops
 
+    if args.w4:
+        return bench_w4(args, dt, dev)
     if args.w8:
         return bench_w8(args, dt, dev)
     for B in args.batches:

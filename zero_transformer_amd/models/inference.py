@@ -20,15 +20,17 @@ import torch.nn.functional as F
 from .. import ops
 from ..ops.reference import alibi_slopes
 from ..utils.config import load_config
-from .quant import W8Weight
+from .quant import W4Weight, W8Weight
 
 
 def _linear(x: torch.Tensor, w, plain=F.linear) -> torch.Tensor:
-    """x @ w^T for a block projection weight: an int8 weight
-    (models/quant.py) goes to ops.linear_w8 whatever the row count, a plain
-    tensor to `plain`."""
+    """x @ w^T for a block projection weight: an int8 or int4 weight
+    (models/quant.py) goes to ops.linear_w8 / ops.linear_w4 whatever the row
+    count, a plain tensor to `plain`."""
     if isinstance(w, W8Weight):
         return ops.linear_w8(x, w.q, w.scale)
+    if isinstance(w, W4Weight):
+        return ops.linear_w4(x, w.packed, w.scale)
     return plain(x, w)
 
 
@@ -115,7 +117,8 @@ class InferenceAttention(nn.Module):
         self.key = nn.Linear(dim, dim, bias=False)
         self.value = nn.Linear(dim, dim, bias=False)
         self.fc_resid = nn.Linear(dim, dim, bias=False)
-        # quantize_w8_ puts the int8 fused weight here and drops query / key / value
+        # quantize_w8_ / quantize_w4_ put the quantized fused weight here and
+        # drop query / key / value
         self.qkv_w8 = None
         if alibi:
             self.register_buffer("slopes", alibi_slopes(heads), persistent=False)
@@ -164,7 +167,7 @@ class InferenceAttention(nn.Module):
             k = k.view(B, T, H, D).transpose(1, 2)
             v = v.view(B, T, H, D).transpose(1, 2)
         else:
-            if self.qkv_w8 is not None:  # row slices of the fused int8 weight
+            if self.qkv_w8 is not None:  # row slices of the fused quantized weight
                 wq, wk, wv = (self.qkv_w8.rows(i * C, (i + 1) * C) for i in range(3))
             else:
                 wq, wk, wv = self.query.weight, self.key.weight, self.value.weight

@@ -382,6 +382,55 @@ def linear_w8(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor) -> torch.Te
     return torch.nn.functional.linear(x, reference.dequantize_rows_w8(q, scale, x.dtype))
 
 
+# rows <= this go to the streaming body of ops/csrc/gemv_w4.hip, more to its
+# MFMA body. Measured (profiles/PERF.md "W4A16 decode"): the streaming body
+# costs 1.5-2 us per extra row and the MFMA body is nearly flat in the rows;
+# summed over the four 1.3B projections the streaming body wins by 20 % at 2
+# rows, ties at 3 (fp16 28.5 vs 28.7 us, bf16 31.2 vs 31.0) and loses by 15 %
+# at 4.
+W4_GEMV_MAX_ROWS = 3
+
+
+def linear_w4(x: torch.Tensor, packed: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """x (..., K) @ W^T -> (..., N) in x's dtype, W = (u - 8) * scale: a
+    linear layer whose weight is stored as 4-bit codes, `packed` uint8
+    (N, K/2), with one fp32 scale per row and group of 128 k, `scale`
+    (N, K/128) (reference.quantize_rows_w4, which also defines the nibble
+    order). Inference only (no autograd).
+
+    GPU, bf16 / fp16, K % 512 == 0, 1..16 rows, grad disabled: the kernels
+    of ops/csrc/gemv_w4.hip, which read the packed weights directly (fp32
+    accumulation, each group's partial sum scaled once, one rounding). GPU
+    with more rows (prefill) or another K: the dequant kernel of the same
+    file writes the weight rounded ONCE to x's dtype into a temporary and
+    F.linear multiplies. The scale varies along K, so no factor can be kept
+    out of the temporary as linear_w8 does: this route is DEFINED as the
+    GEMM over reference.dequantize_rows_w4(packed, scale, x.dtype). CPU:
+    fp32 reference."""
+    if not x.is_cuda:
+        w = reference.dequantize_rows_w4(packed, scale, torch.float32)
+        return torch.nn.functional.linear(x.float(), w).to(x.dtype)
+    ext = hip_ops()
+    N, K = packed.shape[0], 2 * packed.shape[1]
+    rows = x.numel() // K
+    if (
+        x.dtype in (torch.bfloat16, torch.float16)
+        and K % 512 == 0
+        and 1 <= rows <= 16
+        and not torch.is_grad_enabled()
+    ):
+        x2 = x.reshape(rows, K).contiguous()
+        if rows <= W4_GEMV_MAX_ROWS:
+            y = ext.w4_gemv(x2, packed, scale)
+        else:
+            y = ext.w4_gemm(x2, packed, scale)
+        return y.view(*x.shape[:-1], N)
+    if x.dtype in (torch.bfloat16, torch.float16):
+        w = ext.dequant_w4(packed, scale, x.dtype == torch.bfloat16)
+        return torch.nn.functional.linear(x, w)
+    return torch.nn.functional.linear(x, reference.dequantize_rows_w4(packed, scale, x.dtype))
+
+
 def attention_decode(
     q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     slopes: Optional[torch.Tensor],

@@ -37,6 +37,7 @@ SOURCES = [
     "gemm_lt.hip",
     "gemv.hip",
     "gemv_w8.hip",
+    "gemv_w4.hip",
     "sample.hip",
 ]
 
@@ -51,6 +52,7 @@ SOURCE_FLAGS = {
     # products); with the flag, none. The older files keep the flags they
     # were verified with, so that their code objects do not change.
     "gemv_w8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "gemv_w4.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "attn_verify.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 

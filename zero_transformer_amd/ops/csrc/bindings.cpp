@@ -57,6 +57,9 @@ at::Tensor gemv(at::Tensor x, at::Tensor w);
 at::Tensor w8_gemv(at::Tensor x, at::Tensor q, at::Tensor scale);
 at::Tensor w8_gemm(at::Tensor x, at::Tensor q, at::Tensor scale, int64_t ksplit);
 at::Tensor dequant_w8(at::Tensor q, at::Tensor scale, bool bf16);
+at::Tensor w4_gemv(at::Tensor x, at::Tensor packed, at::Tensor scale);
+at::Tensor w4_gemm(at::Tensor x, at::Tensor packed, at::Tensor scale, int64_t ksplit);
+at::Tensor dequant_w4(at::Tensor packed, at::Tensor scale, bool bf16);
 std::vector<at::Tensor> sample_rows(at::Tensor logits, c10::optional<at::Tensor> seen,
                                     at::Tensor temperature, at::Tensor top_k,
                                     at::Tensor top_p, at::Tensor penalty,
@@ -121,6 +124,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("q"), py::arg("scale"), py::arg("ksplit") = 0);
   m.def("dequant_w8", &dequant_w8, "int8 rows * fp32 scale -> bf16 (bf16 = true) or fp16 (gfx950)",
         py::arg("q"), py::arg("scale"), py::arg("bf16"));
+  m.def("w4_gemv", &w4_gemv,
+        "W4A16 group-scaled streaming GEMV x@((u-8)*scale)^T, B <= 4 (gfx950)");
+  // ksplit: 0 = workgroup K split picked from (N, K)
+  m.def("w4_gemm", &w4_gemm,
+        "W4A16 group-scaled skinny MFMA GEMM x@((u-8)*scale)^T, B <= 16 (gfx950)",
+        py::arg("x"), py::arg("packed"), py::arg("scale"), py::arg("ksplit") = 0);
+  m.def("dequant_w4", &dequant_w4,
+        "packed int4 rows * fp32 group scale -> bf16 (bf16 = true) or fp16 (gfx950)",
+        py::arg("packed"), py::arg("scale"), py::arg("bf16"));
   m.def("sample_rows", &sample_rows,
         "fused sort-free sampler, one workgroup per row, per-row options and "
         "counter-based RNG -> {tokens, cut} (gfx950)");

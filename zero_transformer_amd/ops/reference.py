@@ -507,3 +507,53 @@ def quantize_rows_w8(w: torch.Tensor):
 def dequantize_rows_w8(q: torch.Tensor, scale: torch.Tensor, dtype) -> torch.Tensor:
     """q * scale as one fp32 product, rounded once to `dtype`."""
     return (q.float() * scale.float()[:, None]).to(dtype)
+
+
+# ---------------------------------------------------------------------------
+# Weight-only int4 rows, group-scaled ("W4A16", ops/csrc/gemv_w4.hip)
+# ---------------------------------------------------------------------------
+
+W4_GROUP = 128
+# Nibble j (bits 4 j .. 4 j + 3) of little-endian dword d of a row holds the
+# code of k = 8 d + W4_ORDER[j]; byte b of the dword holds nibbles 2 b (low)
+# and 2 b + 1 (high). With this order (dword >> 4 s) & 0x000F000F is the pair
+# (k = 8 d + 2 s, k = 8 d + 2 s + 1), which is what the kernels convert.
+W4_ORDER = (0, 2, 4, 6, 1, 3, 5, 7)
+_W4_POS = (0, 4, 1, 5, 2, 6, 3, 7)  # nibble that holds k = 8 d + i
+
+
+def quantize_rows_w4(w: torch.Tensor, group: int = W4_GROUP):
+    """(N, K) bf16 / fp16 / fp32, K % 128 == 0 -> (packed uint8 (N, K/2),
+    scale fp32 (N, K/128)).
+
+    In fp32, for every row and group of 128 consecutive k: scale = max|w| / 7
+    and q = round_half_even(w / scale) clamped to [-7, 7]; a zero group gets
+    scale 0 and q 0. The stored 4-bit code is u = q + 8 (1..15; code 0, q =
+    -8, is never produced but is decoded). Codes are packed eight to a
+    little-endian dword in the nibble order W4_ORDER above; the order is part
+    of the format a state_dict carries."""
+    assert group == W4_GROUP, "quantize_rows_w4: the kernels read groups of 128"
+    assert w.dim() == 2 and w.shape[1] >= group and w.shape[1] % group == 0, \
+        "quantize_rows_w4: w must be (N, K) with K % 128 == 0"
+    N, K = w.shape
+    wf = w.detach().float().reshape(N, K // group, group)
+    scale = wf.abs().amax(dim=2) / 7.0
+    safe = torch.where(scale > 0, scale, torch.ones_like(scale))
+    u = (torch.round(wf / safe[:, :, None]).clamp_(-7, 7) + 8).to(torch.uint8)
+    nib = u.reshape(N, K // 8, 8)[:, :, list(W4_ORDER)]
+    packed = nib[:, :, 0::2] | (nib[:, :, 1::2] << 4)
+    return packed.reshape(N, K // 2).contiguous(), scale.contiguous()
+
+
+def unpack_rows_w4(packed: torch.Tensor) -> torch.Tensor:
+    """packed uint8 (N, K/2) -> q int8 (N, K) in -8..7 (all 16 codes)."""
+    N, K2 = packed.shape
+    b = packed.reshape(N, K2 // 4, 4)
+    nib = torch.stack([b & 15, b >> 4], dim=3).reshape(N, K2 // 4, 8)
+    return (nib[:, :, list(_W4_POS)].to(torch.int8) - 8).reshape(N, 2 * K2)
+
+
+def dequantize_rows_w4(packed: torch.Tensor, scale: torch.Tensor, dtype) -> torch.Tensor:
+    """(u - 8) * scale of the group as one fp32 product, rounded once to `dtype`."""
+    q = unpack_rows_w4(packed).float()
+    return (q * scale.float().repeat_interleave(W4_GROUP, dim=1)).to(dtype)
