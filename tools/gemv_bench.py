@@ -3,6 +3,7 @@
     python tools/gemv_bench.py [--dtype fp16] [--iters 200]
     python tools/gemv_bench.py --w8 [--batches 1 2 3 4 8 16] [--rounds 5]
     python tools/gemv_bench.py --w4 [--batches 1 2 3 4 8 16] [--ksplit 2 4]
+    python tools/gemv_bench.py --rows --batches 17 32 48 64 [--ksplit 1 2 8]
 
 Compares ops/csrc/gemv.hip against torch F.linear (hipBLASLt) on the 1.3B
 decode shapes. The weight stream is the bound (profiles/PERF.md): report
@@ -121,8 +122,48 @@ def bench_w4(args, dt, dev):
             print(f"N={N:5d} K={K:5d} rows={B:2d}: " + " | ".join(cells), flush=True)
 
 
+def bench_rows(args, dt, dev):
+    """The 17..64-row body of ops/csrc/gemm_wq_rows.hip, both formats, next to
+    the dequant + F.linear route the same call took before it (linear_w8 /
+    linear_w4 with grad enabled still take it) and to 16-bit decode_linear,
+    the sides alternating over --rounds; the median per side in us."""
+    from zero_transformer_amd import ops
+    from zero_transformer_amd.ops.reference import quantize_rows_w4, quantize_rows_w8
+
+    ext = ops.hip_ops()
+    print(f"quantized rows 17-64 ({args.dtype}); median us")
+    for N, K in W8_SHAPES:
+        w = torch.randn(N, K, device=dev, dtype=dt) * 0.02
+        q, scale = quantize_rows_w8(w)
+        p4, s4 = quantize_rows_w4(w)
+        for B in args.batches:
+            x = torch.randn(B, K, device=dev, dtype=dt)
+
+            def library(fn, *a):
+                with torch.enable_grad():
+                    return fn(x, *a)
+
+            sides = {"w16": lambda: ops.decode_linear(x, w),
+                     "w8_dequant+linear": lambda: library(ops.linear_w8, q, scale),
+                     "w8_rows": lambda: ext.w8_gemm_rows(x, q, scale),
+                     "w4_dequant+linear": lambda: library(ops.linear_w4, p4, s4),
+                     "w4_rows": lambda: ext.w4_gemm_rows(x, p4, s4)}
+            for ks in (k for k in args.ksplit if k <= K // 512):
+                sides[f"w8_rows/ks{ks}"] = lambda ks=ks: ext.w8_gemm_rows(x, q, scale, ks)
+                sides[f"w4_rows/ks{ks}"] = lambda ks=ks: ext.w4_gemm_rows(x, p4, s4, ks)
+            times = {k: [] for k in sides}
+            for _ in range(args.rounds):
+                for k, fn in sides.items():
+                    times[k].append(bench(fn, args.iters))
+            cells = [f"{k} {sorted(ts)[len(ts) // 2]*1e6:6.2f}" for k, ts in times.items()]
+            print(f"N={N:5d} K={K:5d} rows={B:2d}: " + " | ".join(cells), flush=True)
+
+
 def main():
     p = argparse.ArgumentParser()
+    p.add_argument("--rows", action="store_true",
+                   help="time ops/csrc/gemm_wq_rows.hip (--batches 17..64) next to the "
+                        "dequant + F.linear route and the 16-bit path")
     p.add_argument("--w8", action="store_true",
                    help="time ops/csrc/gemv_w8.hip next to the 16-bit decode paths")
     p.add_argument("--w4", action="store_true",
@@ -138,6 +179,8 @@ def main():
     dev = torch.device("cuda", 0)
     from zero_transformer_amd import ops
 
+    if args.rows:
+        return bench_rows(args, dt, dev)
     if args.w4:
         return bench_w4(args, dt, dev)
     if args.w8:

@@ -339,6 +339,11 @@ def decode_linear(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
 # wins up to 3 rows on all four 1.3B shapes and at 4 rows on three of them.
 W8_GEMV_MAX_ROWS = 4
 
+# 17..this many rows go to the fused-dequant MFMA body of
+# ops/csrc/gemm_wq_rows.hip (both formats), more rows to the dequant +
+# F.linear route. Measured: profiles/PERF.md "Quantized rows 17-64".
+WQ_ROWS_MAX = 64
+
 
 def linear_w8(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     """x (..., K) @ (q (N, K) int8 * scale (N,) fp32)^T -> (..., N) in x's
@@ -348,8 +353,10 @@ def linear_w8(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor) -> torch.Te
 
     GPU, bf16 / fp16, K % 512 == 0, 1..16 rows, grad disabled: the kernels
     of ops/csrc/gemv_w8.hip, which read the int8 weights directly (fp32
-    accumulation, scale applied once to the sum, one rounding). GPU with
-    more rows (prefill) or another K: scale[n] = f[n] * 2^e[n] with f in
+    accumulation, scale applied once to the sum, one rounding). 17..64 rows
+    under the same conditions: the fused-dequant MFMA body of
+    ops/csrc/gemm_wq_rows.hip, same formula. GPU with more rows (prefill),
+    another K or grad enabled: scale[n] = f[n] * 2^e[n] with f in
     [1, 2); the dequant kernel of the same file writes q * 2^e (exact in
     bf16 / fp16) into a temporary, F.linear multiplies, and the columns get
     the factor f in fp32. The GEMM's 16-bit output is y / f, no larger than
@@ -370,6 +377,14 @@ def linear_w8(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor) -> torch.Te
     ):
         x2 = x.reshape(rows, K).contiguous()
         y = ext.w8_gemv(x2, q, scale) if rows <= W8_GEMV_MAX_ROWS else ext.w8_gemm(x2, q, scale)
+        return y.view(*x.shape[:-1], N)
+    if (
+        x.dtype in (torch.bfloat16, torch.float16)
+        and K % 512 == 0
+        and 16 < rows <= WQ_ROWS_MAX
+        and not torch.is_grad_enabled()
+    ):
+        y = ext.w8_gemm_rows(x.reshape(rows, K).contiguous(), q, scale)
         return y.view(*x.shape[:-1], N)
     if x.dtype in (torch.bfloat16, torch.float16) and K % 16 == 0:
         # 2^e clamped so that q * 2^e is a normal number of the type (|q| >= 1
@@ -401,12 +416,15 @@ def linear_w4(x: torch.Tensor, packed: torch.Tensor, scale: torch.Tensor) -> tor
     GPU, bf16 / fp16, K % 512 == 0, 1..16 rows, grad disabled: the kernels
     of ops/csrc/gemv_w4.hip, which read the packed weights directly (fp32
     accumulation, each group's partial sum scaled once, one rounding). GPU
-    with more rows (prefill) or another K: the dequant kernel of the same
-    file writes the weight rounded ONCE to x's dtype into a temporary and
-    F.linear multiplies. The scale varies along K, so no factor can be kept
-    out of the temporary as linear_w8 does: this route is DEFINED as the
-    GEMM over reference.dequantize_rows_w4(packed, scale, x.dtype). CPU:
-    fp32 reference."""
+    with more rows (prefill), another K or grad enabled: the dequant kernel
+    of the same file writes the weight rounded ONCE to x's dtype into a
+    temporary and F.linear multiplies. The scale varies along K, so no
+    factor can be kept out of the temporary as linear_w8 does: the many-row
+    result is DEFINED as the GEMM over reference.dequantize_rows_w4(packed,
+    scale, x.dtype). 17..64 rows, K % 512 == 0, grad disabled: the
+    fused-dequant MFMA body of ops/csrc/gemm_wq_rows.hip computes that same
+    product (it makes the once-rounded weight in registers, bit for bit, and
+    accumulates in fp32) without the temporary. CPU: fp32 reference."""
     if not x.is_cuda:
         w = reference.dequantize_rows_w4(packed, scale, torch.float32)
         return torch.nn.functional.linear(x.float(), w).to(x.dtype)
@@ -424,6 +442,14 @@ def linear_w4(x: torch.Tensor, packed: torch.Tensor, scale: torch.Tensor) -> tor
             y = ext.w4_gemv(x2, packed, scale)
         else:
             y = ext.w4_gemm(x2, packed, scale)
+        return y.view(*x.shape[:-1], N)
+    if (
+        x.dtype in (torch.bfloat16, torch.float16)
+        and K % 512 == 0
+        and 16 < rows <= WQ_ROWS_MAX
+        and not torch.is_grad_enabled()
+    ):
+        y = ext.w4_gemm_rows(x.reshape(rows, K).contiguous(), packed, scale)
         return y.view(*x.shape[:-1], N)
     if x.dtype in (torch.bfloat16, torch.float16):
         w = ext.dequant_w4(packed, scale, x.dtype == torch.bfloat16)

@@ -60,6 +60,8 @@ at::Tensor dequant_w8(at::Tensor q, at::Tensor scale, bool bf16);
 at::Tensor w4_gemv(at::Tensor x, at::Tensor packed, at::Tensor scale);
 at::Tensor w4_gemm(at::Tensor x, at::Tensor packed, at::Tensor scale, int64_t ksplit);
 at::Tensor dequant_w4(at::Tensor packed, at::Tensor scale, bool bf16);
+at::Tensor w8_gemm_rows(at::Tensor x, at::Tensor q, at::Tensor scale, int64_t ksplit);
+at::Tensor w4_gemm_rows(at::Tensor x, at::Tensor packed, at::Tensor scale, int64_t ksplit);
 std::vector<at::Tensor> sample_rows(at::Tensor logits, c10::optional<at::Tensor> seen,
                                     at::Tensor temperature, at::Tensor top_k,
                                     at::Tensor top_p, at::Tensor penalty,
@@ -133,6 +135,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dequant_w4", &dequant_w4,
         "packed int4 rows * fp32 group scale -> bf16 (bf16 = true) or fp16 (gfx950)",
         py::arg("packed"), py::arg("scale"), py::arg("bf16"));
+  // ksplit: 0 = workgroup K split picked from (N, K)
+  m.def("w8_gemm_rows", &w8_gemm_rows,
+        "W8A16 fused-dequant MFMA GEMM x@(q*scale)^T, B <= 64 (gfx950)",
+        py::arg("x"), py::arg("q"), py::arg("scale"), py::arg("ksplit") = 0);
+  m.def("w4_gemm_rows", &w4_gemm_rows,
+        "W4A16 fused-dequant MFMA GEMM over the once-rounded weight, B <= 64 (gfx950)",
+        py::arg("x"), py::arg("packed"), py::arg("scale"), py::arg("ksplit") = 0);
   m.def("sample_rows", &sample_rows,
         "fused sort-free sampler, one workgroup per row, per-row options and "
         "counter-based RNG -> {tokens, cut} (gfx950)");
