@@ -234,6 +234,9 @@ def main():
                    help="--paged: sequences decoded per step")
     p.add_argument("--kv-pages", type=int, default=256,
                    help="--paged: pages of 64 rows in the KV pool (page 0 is reserved)")
+    p.add_argument("--kv8", action="store_true",
+                   help="--paged: int8 KV cache with one fp32 scale per row and "
+                        "head: about half the cache bytes per row")
     p.add_argument("--w8", action="store_true",
                    help="weight-only int8 block projections (W8A16): half the "
                         "weight bytes per decode step")
@@ -280,7 +283,8 @@ def main():
 
             opts = {k: v for k, v in kw.items() if k != "max_new_tokens"}
             engine = ServingEngine(model, args.slots, args.kv_pages,
-                                   eos_token=getattr(tok, "eos_token_id", None), **opts)
+                                   eos_token=getattr(tok, "eos_token_id", None),
+                                   kv_int8=args.kv8, **opts)
         app = build_app(model, tok, device, engine)
         uvicorn.run(app, host=args.host, port=args.port)
     else:

@@ -77,6 +77,10 @@ def main():
                    "and the server defaults; median of --runs rounds")
     p.add_argument("--kv-pages", type=int, default=0,
                    help="pages in the pool (0: what --batch full-length requests need)")
+    p.add_argument("--kv8", action="store_true",
+                   help="with --fast --paged: next to the 16-bit engine, one on the "
+                   "int8 KV cache (ServingEngine(kv_int8=True)), and how many of "
+                   "its tokens agree with the 16-bit engine's")
     p.add_argument("--prefill-chunk", type=int, default=None)
     p.add_argument("--runs", type=int, default=15)
     p.add_argument("--w8", action="store_true",
@@ -165,7 +169,7 @@ def main():
             prompts = idx.tolist()
         rows = max(len(pr) for pr in prompts) + args.tokens
         pages = args.kv_pages or args.batch * -(-min(rows, model.num_ctx) // 64) + 1
-        reuse = []
+        reuse, kv8, tokens = [], [False], {}
 
         @torch.no_grad()
         def run():
@@ -173,10 +177,13 @@ def main():
             # and its graph capture; the second figure reuses the engine
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            eng = ServingEngine(model, args.batch, pages, prefix_cache=False)
+            eng = ServingEngine(model, args.batch, pages, prefix_cache=False,
+                                kv_int8=kv8[0])
             for pr in prompts:
                 eng.submit(pr, args.tokens)
-            n = sum(len(r) for r in eng.run().values())
+            out = eng.run()
+            tokens[kv8[0]] = [out[i] for i in sorted(out)]
+            n = sum(len(r) for r in out.values())
             torch.cuda.synchronize()
             t1 = time.perf_counter()
             for pr in prompts:
@@ -200,6 +207,15 @@ def main():
     print(f"{args.model_size} {args.dtype} batch {args.batch} {mode}: "
           f"{tps * args.batch:.1f} tokens/s ({1e3 / tps:.2f} ms/token)"
           + (f"; engine reused {reuse[-1]:.1f} tokens/s" if args.paged else ""))
+    if args.paged and args.kv8:
+        kv8[0] = True
+        run()
+        tps = run()
+        pairs = [(a, b) for x, y in zip(tokens[False], tokens[True]) for a, b in zip(x, y)]
+        print(f"{args.model_size} {args.dtype} batch {args.batch} {mode} int8 KV: "
+              f"{tps * args.batch:.1f} tokens/s ({1e3 / tps:.2f} ms/token); engine reused "
+              f"{reuse[-1]:.1f} tokens/s; {sum(a == b for a, b in pairs)} of {len(pairs)} "
+              f"tokens agree with the 16-bit cache")
 
 
 SERVER_DEFAULTS = dict(temperature=0.8, top_k=0, top_p=0.95, repetition_penalty=1.1)

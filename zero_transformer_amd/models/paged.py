@@ -5,7 +5,8 @@ pages, (P, H, R, D) per layer, and a per-slot block table: a sequence holds
 ceil(rows / R) pages wherever they are free, and two sequences with the same
 prompt prefix can point at the same pages. Both attention kernels address the
 pool through the table (ops.attention_prefill_paged /
-ops.attention_decode_paged, ops/csrc/attn_paged.hip).
+ops.attention_decode_paged, ops/csrc/attn_paged.hip). PagedKVCacheQ8 is the
+same cache with int8 pools and per-row scales (ops/csrc/attn_kv8.hip).
 
 ServingEngine keeps a fixed number of slots decoding in one (optionally
 hipGraph-captured) step and changes the population between steps: finished
@@ -47,16 +48,67 @@ class _PagedAttend:
             self.block_table, lens, start)
 
 
+class _PagedAttendQ8:
+    """_PagedAttend for an int8 cache (ops/csrc/attn_kv8.hip): uint8 pools
+    `k` / `v` with per-row scale pools `k_scale` / `v_scale`, and a 16-bit
+    staging pair `stage_k` / `stage_v` (B, H, M*R, D) shared by all layers.
+
+    Decode attends on the codes natively. Prefill and verify quantize the new
+    rows into the pool (which also replaces them in qkv by what the pool now
+    holds), dequantize the rows already cached into the staging pair, and run
+    the contiguous 16-bit kernels there: those append qkv's rows behind the
+    cached ones in the staging pair and attend over both."""
+
+    def attend_decode(self, layer_idx, qkv, num_head, slopes):
+        return ops.attention_decode_paged_q8(
+            qkv, self.k[layer_idx], self.v[layer_idx], self.k_scale[layer_idx],
+            self.v_scale[layer_idx], num_head, slopes, self.block_table, self.len_t)
+
+    def _stage(self, layer_idx, qkv, lens, start):
+        pools = (self.k[layer_idx], self.v[layer_idx],
+                 self.k_scale[layer_idx], self.v_scale[layer_idx])
+        qkv = qkv.contiguous()
+        ops.kv8_quantize_paged(qkv, *pools, self.block_table, lens, start)
+        ops.kv8_load_paged(*pools, self.block_table, start, self.stage_k, self.stage_v)
+        return qkv
+
+    def attend_prefill(self, layer_idx, qkv, num_head, slopes, lens, start):
+        qkv = self._stage(layer_idx, qkv, lens, start)
+        return ops.attention_prefill_append(
+            qkv, self.stage_k, self.stage_v, num_head, slopes, lens, start)
+
+    def attend_verify(self, layer_idx, qkv, num_head, slopes, lens, start):
+        qkv = self._stage(layer_idx, qkv, lens, start)
+        return ops.attention_verify_append(
+            qkv, self.stage_k, self.stage_v, num_head, slopes, lens, start)
+
+
+def _view_init(view, cache, slots: Sequence[int], lens) -> None:
+    sel = torch.as_tensor(list(slots), dtype=torch.long, device=cache.block_table.device)
+    view.k, view.v = cache.k, cache.v
+    view.block_table = cache.block_table.index_select(0, sel).contiguous()
+    view.len_t = torch.as_tensor(lens, dtype=torch.int32).to(sel.device)
+
+
 class _SlotView(_PagedAttend):
     """Some slots of a PagedKVCache, for a prefill of just those: the same
     pools (they have no batch dimension) with the slots' table and length
     rows."""
 
     def __init__(self, cache: "PagedKVCache", slots: Sequence[int], lens):
-        sel = torch.as_tensor(list(slots), dtype=torch.long, device=cache.block_table.device)
-        self.k, self.v = cache.k, cache.v
-        self.block_table = cache.block_table.index_select(0, sel).contiguous()
-        self.len_t = torch.as_tensor(lens, dtype=torch.int32).to(sel.device)
+        _view_init(self, cache, slots, lens)
+
+
+class _SlotViewQ8(_PagedAttendQ8):
+    """_SlotView of a PagedKVCacheQ8: also the scale pools, and as many rows
+    of the staging pair as there are slots in the view (the pair is scratch:
+    every call fills what it reads)."""
+
+    def __init__(self, cache: "PagedKVCacheQ8", slots: Sequence[int], lens):
+        _view_init(self, cache, slots, lens)
+        self.k_scale, self.v_scale = cache.k_scale, cache.v_scale
+        self.stage_k = cache.stage_k[: len(slots)]
+        self.stage_v = cache.stage_v[: len(slots)]
 
 
 class PagedKVCache(_PagedAttend):
@@ -188,6 +240,36 @@ class PagedKVCache(_PagedAttend):
         return _SlotView(self, slots, lens)
 
 
+class PagedKVCacheQ8(_PagedAttendQ8, PagedKVCache):
+    """PagedKVCache with int8 pools: a cached row costs D + 4 bytes per head
+    instead of 2 D. `k` / `v` hold the codes (uint8, u = q + 128), `k_scale` /
+    `v_scale` (P, H, R) fp32 one scale per row and head (format and quantizer:
+    ops.kv8_quantize_paged). `dtype` is the model's: that of the one staging
+    pair (slots, H, M*R, D) the prefill and verify passes of all layers work
+    in. Allocator, table and lengths are the parent's."""
+
+    def __init__(self, n_layers: int, slots: int, heads: int, head_dim: int,
+                 num_pages: int, page_rows: int, max_pages_per_seq: int,
+                 device, dtype):
+        super().__init__(n_layers, slots, heads, head_dim, num_pages, page_rows,
+                         max_pages_per_seq, device, torch.uint8)
+        for pool in self.k + self.v:
+            pool.fill_(128)  # code of 0, as the 16-bit pools start at 0
+        shape = (num_pages, heads, page_rows)
+        self.k_scale = [torch.zeros(shape, device=device) for _ in range(n_layers)]
+        self.v_scale = [torch.zeros(shape, device=device) for _ in range(n_layers)]
+        stage = (slots, heads, max_pages_per_seq * page_rows, head_dim)
+        self.stage_k = torch.zeros(stage, device=device, dtype=dtype)
+        self.stage_v = torch.zeros(stage, device=device, dtype=dtype)
+
+    def kv_bytes(self) -> int:
+        return sum(t.numel() * t.element_size()
+                   for t in self.k + self.v + self.k_scale + self.v_scale)
+
+    def view(self, slots: Sequence[int], lens) -> _SlotViewQ8:
+        return _SlotViewQ8(self, slots, lens)
+
+
 class _Request:
     __slots__ = ("rid", "prompt", "limit", "slot", "shared", "keys",
                  "temperature", "top_k", "top_p", "penalty", "seed")
@@ -257,6 +339,11 @@ class ServingEngine:
     Decode appends never land in a shared page
     (only full prompt pages are shared). Keyed pages of retired requests stay
     cached until free pages run short, then go least recently used first.
+
+    `kv_int8=True` keeps the cache as int8 codes with one fp32 scale per row
+    and head (PagedKVCacheQ8): about half the bytes per cached row, read
+    natively by the decode attention. Every pass attends over the dequantized
+    values, so tokens can differ from the 16-bit cache's.
     """
 
     @torch.no_grad()
@@ -265,14 +352,16 @@ class ServingEngine:
                  temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
                  repetition_penalty: float = 1.0, use_graph: bool = True,
                  prefill_chunk: Optional[int] = None,
-                 check_every: int = FINISHED_CHECK_EVERY, prefix_cache: bool = True):
+                 check_every: int = FINISHED_CHECK_EVERY, prefix_cache: bool = True,
+                 kv_int8: bool = False):
         p = next(model.parameters())
         dev = p.device
         attn = model.blocks[0].attn
         self.model, self.dev = model, dev
-        self.cache = PagedKVCache(model.N, slots, attn.num_head, attn.head_dim,
-                                  num_pages, page_rows, -(-model.num_ctx // page_rows),
-                                  dev, p.dtype)
+        cache_cls = PagedKVCacheQ8 if kv_int8 else PagedKVCache
+        self.cache = cache_cls(model.N, slots, attn.num_head, attn.head_dim,
+                               num_pages, page_rows, -(-model.num_ctx // page_rows),
+                               dev, p.dtype)
         self.eos_token = eos_token
         self.sampling = (temperature, top_k, top_p, repetition_penalty, sample)
         self._check_options(temperature, top_k, top_p, repetition_penalty)

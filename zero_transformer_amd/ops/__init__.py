@@ -661,6 +661,94 @@ def attention_decode_paged(
 
 
 # ---------------------------------------------------------------------------
+# Int8 paged KV cache (ops/csrc/attn_kv8.hip)
+# ---------------------------------------------------------------------------
+
+
+def _kv8_on_gpu(t: torch.Tensor, k_pool: torch.Tensor) -> bool:
+    return (
+        t.is_cuda
+        and t.dtype in (torch.float16, torch.bfloat16)
+        and k_pool.shape[3] in (32, 64, 96, 128)
+    )
+
+
+def kv8_quantize_paged(
+    qkv: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor,
+    k_scale: torch.Tensor, v_scale: torch.Tensor, block_table: torch.Tensor,
+    lens: Optional[torch.Tensor] = None, start: Optional[torch.Tensor] = None,
+) -> None:
+    """The append of an int8 paged KV cache: qkv (B,T,3C) contiguous, k_pool /
+    v_pool (P,H,R,D) uint8, k_scale / v_scale (P,H,R) fp32, all written in
+    place.
+
+    A stored code is u = q + 128 with q in [-127, 127] and stands for
+    (u - 128) * scale; scale = max_d |x| / 127 per row and head and
+    q = round_half_even(x / scale), in fp32 (reference.quantize_kv_rows; a
+    zero row has scale 0 and codes 128). `block_table`, `lens`, `start` and
+    their clamps are those of attention_prefill_paged: the K and V columns of
+    rows i < n go to logical rows start[b]+i, and no other pool byte or scale
+    is written. The same columns of qkv are overwritten by their dequantized
+    value, rounded once to qkv's dtype, so that a 16-bit attention over qkv
+    sees what the cache holds; Q and rows >= n stay. GPU: fp16/bf16, head_dim
+    32/64/96/128 (R % 64 != 0 raises), bit-equal to the fp32 reference, which
+    everything else takes. Inference only (no autograd)."""
+    assert qkv.is_contiguous(), "kv8_quantize_paged writes qkv in place: contiguous only"
+    if not _kv8_on_gpu(qkv, k_pool):
+        return reference.kv8_quantize_paged(
+            qkv, k_pool, v_pool, k_scale, v_scale, block_table, lens, start)
+    B, T = qkv.shape[:2]
+    if lens is None:
+        lens = torch.full((B,), T, dtype=torch.int32, device=qkv.device)
+    if start is None:
+        start = torch.zeros(B, dtype=torch.int32, device=qkv.device)
+    hip_ops().kv8_quantize_paged(
+        qkv, k_pool, v_pool, k_scale, v_scale, block_table, lens, start)
+
+
+def kv8_load_paged(
+    k_pool: torch.Tensor, v_pool: torch.Tensor, k_scale: torch.Tensor,
+    v_scale: torch.Tensor, block_table: torch.Tensor, rows: torch.Tensor,
+    k_dst: torch.Tensor, v_dst: torch.Tensor,
+) -> None:
+    """Dequantize the head of each sequence of an int8 paged KV cache (layout
+    as in kv8_quantize_paged) into contiguous caches: rows [0, min(rows[b], S,
+    M*R)) of k_dst / v_dst (B,H,S,D) <- (u - 128) * scale, one fp32 product
+    rounded once to their dtype; other rows are untouched. `rows`: (B,) int32
+    on the device, read in-kernel. GPU: fp16/bf16 destinations, head_dim
+    32/64/96/128; everything else takes the fp32 reference."""
+    if not _kv8_on_gpu(k_dst, k_pool):
+        return reference.kv8_load_paged(
+            k_pool, v_pool, k_scale, v_scale, block_table, rows, k_dst, v_dst)
+    hip_ops().kv8_load_paged(
+        k_pool, v_pool, k_scale, v_scale, block_table, rows, k_dst, v_dst)
+
+
+def attention_decode_paged_q8(
+    qkv: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor,
+    k_scale: torch.Tensor, v_scale: torch.Tensor, num_head: int,
+    slopes: Optional[torch.Tensor], block_table: torch.Tensor, lens: torch.Tensor,
+) -> torch.Tensor:
+    """attention_decode_paged on an int8 paged KV cache (layout and quantizer
+    as in kv8_quantize_paged): qkv (B,1,3C) -> (B,1,C). The new k/v row is
+    quantized and stored at logical row lens[b]-1, and sequence b attends over
+    the values (u - 128) * scale of its rows [0, lens[b]), the new one
+    included, taken in fp32. `lens` and `block_table` are read in-kernel (no
+    host sync, graph-replayable); lens[b] == 0 writes nothing and returns
+    zeros. The result is deterministic and does not depend on R or on which
+    pages the table names. GPU: fp16/bf16, head_dim 32/64/96/128 (R % 64 != 0
+    raises); everything else takes the fp32 reference. Inference only."""
+    if not _kv8_on_gpu(qkv, k_pool):
+        return reference.attention_decode_paged_q8(
+            qkv, k_pool, v_pool, k_scale, v_scale, num_head, slopes, block_table, lens)
+    assert k_pool.shape[1] == num_head, "k_pool heads != num_head"
+    if slopes is None:
+        slopes = torch.zeros(num_head, dtype=torch.float32, device=qkv.device)
+    return hip_ops().attn_decode_paged_q8(
+        qkv.contiguous(), k_pool, v_pool, k_scale, v_scale, slopes, block_table, lens)
+
+
+# ---------------------------------------------------------------------------
 # Fused per-row sampler
 # ---------------------------------------------------------------------------
 

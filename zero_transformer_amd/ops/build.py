@@ -33,6 +33,7 @@ SOURCES = [
     "attn_prefill.hip",
     "attn_paged.hip",
     "attn_verify.hip",
+    "attn_kv8.hip",
     "attention_bwd.hip",
     "gemm_lt.hip",
     "gemv.hip",
@@ -56,6 +57,7 @@ SOURCE_FLAGS = {
     "gemv_w4.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "gemm_wq_rows.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "attn_verify.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "attn_kv8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

@@ -47,6 +47,15 @@ at::Tensor attn_verify_append(at::Tensor qkv, at::Tensor k_cache,
 at::Tensor attn_verify_paged(at::Tensor qkv, at::Tensor k_pool, at::Tensor v_pool,
                              at::Tensor slopes, at::Tensor block_table,
                              at::Tensor lens, at::Tensor start);
+void kv8_quantize_paged(at::Tensor qkv, at::Tensor k_pool, at::Tensor v_pool,
+                        at::Tensor k_scale, at::Tensor v_scale, at::Tensor block_table,
+                        at::Tensor lens, at::Tensor start);
+void kv8_load_paged(at::Tensor k_pool, at::Tensor v_pool, at::Tensor k_scale,
+                    at::Tensor v_scale, at::Tensor block_table, at::Tensor rows,
+                    at::Tensor k_dst, at::Tensor v_dst);
+at::Tensor attn_decode_paged_q8(at::Tensor qkv, at::Tensor k_pool, at::Tensor v_pool,
+                                at::Tensor k_scale, at::Tensor v_scale, at::Tensor slopes,
+                                at::Tensor block_table, at::Tensor lens);
 std::vector<at::Tensor> attn_fwd(at::Tensor qkv, at::Tensor slopes, int64_t H,
                                  double p_drop, int64_t seed);
 std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor qkv, at::Tensor slopes,
@@ -109,6 +118,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_verify_paged", &attn_verify_paged,
         "attn_verify_append on a paged KV pool (P, H, R, D) addressed through a "
         "(B, M) block table (gfx950 MFMA)");
+  m.def("kv8_quantize_paged", &kv8_quantize_paged,
+        "quantize the K/V columns of qkv rows into an int8 paged KV pool with "
+        "per-row scales, and replace them in qkv by their dequantized value (gfx950)");
+  m.def("kv8_load_paged", &kv8_load_paged,
+        "dequantize the first rows of an int8 paged KV pool into contiguous "
+        "16-bit caches (gfx950)");
+  m.def("attn_decode_paged_q8", &attn_decode_paged_q8,
+        "attn_decode_paged on an int8 paged KV pool with per-row scales; "
+        "quantizes and appends the new row (gfx950)");
   m.def("attn_fwd", &attn_fwd, "fused causal ALiBi flash attention fwd (gfx950 MFMA)");
   // fused: -1 = process default (ZTA_BWD_FUSED), 0 = two-kernel dq + dkdv,
   // 1 = single fused kernel (head_dim 128; other dims take the two-kernel path)

@@ -510,6 +510,111 @@ def dequantize_rows_w8(q: torch.Tensor, scale: torch.Tensor, dtype) -> torch.Ten
 
 
 # ---------------------------------------------------------------------------
+# Int8 paged KV cache (ops/csrc/attn_kv8.hip)
+# ---------------------------------------------------------------------------
+
+
+def quantize_kv_rows(x: torch.Tensor):
+    """(..., D) bf16 / fp16 / fp32 -> (u uint8 (..., D), scale fp32 (...)).
+
+    quantize_rows_w8's rule per row of the last dimension, stored unsigned: in
+    fp32, scale = max_d |x| / 127 and u = 128 + round_half_even(x / scale)
+    clamped to [1, 255]. A zero row gets scale 0 and every code 128. The value
+    a code stands for is (u - 128) * scale."""
+    xf = x.detach().float()
+    scale = xf.abs().amax(dim=-1) / 127.0
+    safe = torch.where(scale > 0, scale, torch.ones_like(scale))
+    q = torch.round(xf / safe.unsqueeze(-1)).clamp_(-127, 127)
+    return (q + 128).to(torch.uint8).contiguous(), scale
+
+
+def dequantize_kv_rows(u: torch.Tensor, scale: torch.Tensor, dtype) -> torch.Tensor:
+    """(u - 128) * scale as one fp32 product, rounded once to `dtype`."""
+    return ((u.float() - 128.0) * scale.float().unsqueeze(-1)).to(dtype)
+
+
+def _paged_rows(block_table, P: int, R: int, b: int, lo: int, hi: int):
+    """(page, row in page) index tensors of sequence b's logical rows [lo, hi)."""
+    j = torch.arange(lo, hi, device=block_table.device)
+    return block_table[b].long()[j // R].clamp(0, P - 1), j % R
+
+
+def kv8_quantize_paged(qkv, k_pool, v_pool, k_scale, v_scale, block_table,
+                       lens=None, start=None) -> None:
+    """ops.kv8_quantize_paged, one sequence at a time: the K / V columns of
+    qkv rows i < n go, quantized per head, to logical rows st + i of the uint8
+    pools (P, H, R, D) and scale pools (P, H, R), and are replaced in qkv by
+    their dequantized value. (st, n) as in attention_prefill_append with
+    S_alloc = M * R. Nothing else is written."""
+    B, T, C3 = qkv.shape
+    C = C3 // 3
+    P, H, R, D = k_pool.shape
+    S_alloc = block_table.shape[1] * R
+    lens_l = [T] * B if lens is None else lens.tolist()
+    start_l = [0] * B if start is None else start.tolist()
+    for b in range(B):
+        st = min(max(int(start_l[b]), 0), S_alloc)
+        n = min(max(int(lens_l[b]), 0), min(T, S_alloc - st))
+        if n == 0:
+            continue
+        page, r = _paged_rows(block_table, P, R, b, st, st + n)
+        for col, pool, sc in ((C, k_pool, k_scale), (2 * C, v_pool, v_scale)):
+            x = qkv[b, :n, col:col + C].reshape(n, H, D)
+            u, s = quantize_kv_rows(x)
+            pool[page, :, r] = u
+            sc[page, :, r] = s
+            qkv[b, :n, col:col + C] = dequantize_kv_rows(u, s, qkv.dtype).reshape(n, C)
+
+
+def kv8_load_paged(k_pool, v_pool, k_scale, v_scale, block_table, rows,
+                   k_dst, v_dst) -> None:
+    """ops.kv8_load_paged: rows [0, min(rows[b], S, M * R)) of the contiguous
+    k_dst / v_dst (B, H, S, D) <- the dequantized logical rows of sequence b;
+    other rows stay."""
+    P, H, R, D = k_pool.shape
+    S = k_dst.shape[2]
+    for b, n in enumerate(rows.tolist()):
+        n = min(max(int(n), 0), S, block_table.shape[1] * R)
+        page, r = _paged_rows(block_table, P, R, b, 0, n)
+        for pool, sc, dst in ((k_pool, k_scale, k_dst), (v_pool, v_scale, v_dst)):
+            dst[b, :, :n] = dequantize_kv_rows(
+                pool[page, :, r], sc[page, :, r], dst.dtype).transpose(0, 1)
+
+
+def attention_decode_paged_q8(qkv, k_pool, v_pool, k_scale, v_scale, num_head,
+                              slopes, block_table, lens) -> torch.Tensor:
+    """attention_decode_paged on an int8 paged cache: the new K / V row is
+    quantized (quantize_kv_rows), stored at logical row lens[b] - 1, and
+    sequence b attends over the fp32 values (u - 128) * scale of its rows
+    [0, lens[b]). Gather and dequantize, the contiguous reference on the
+    quantized new row, then the codes and scales of the written rows;
+    lens[b] == 0 writes nothing and returns zeros."""
+    B, _, C3 = qkv.shape
+    C = C3 // 3
+    P, H, R, D = k_pool.shape
+    S_alloc = block_table.shape[1] * R
+    new = [quantize_kv_rows(t.reshape(B, H, D)) for t in qkv.split(C, dim=-1)[1:]]
+    qf = qkv.float().clone()
+    for i, (u, s) in enumerate(new):
+        qf[:, 0, (1 + i) * C:(2 + i) * C] = dequantize_kv_rows(u, s, torch.float32).reshape(B, C)
+    k = dequantize_kv_rows(paged_gather(k_pool, block_table),
+                           paged_gather(k_scale.unsqueeze(-1), block_table).squeeze(-1),
+                           torch.float32)
+    v = dequantize_kv_rows(paged_gather(v_pool, block_table),
+                           paged_gather(v_scale.unsqueeze(-1), block_table).squeeze(-1),
+                           torch.float32)
+    out = attention_decode_append(qf, k, v, num_head, slopes, lens)
+    for b, S in enumerate(lens.tolist()):
+        S = min(max(int(S), 0), S_alloc)
+        if S:
+            page, r = _paged_rows(block_table, P, R, b, S - 1, S)
+            for (u, s), pool, sc in zip(new, (k_pool, v_pool), (k_scale, v_scale)):
+                pool[page, :, r] = u[b].unsqueeze(0)
+                sc[page, :, r] = s[b].unsqueeze(0)
+    return out.to(qkv.dtype)
+
+
+# ---------------------------------------------------------------------------
 # Weight-only int4 rows, group-scaled ("W4A16", ops/csrc/gemv_w4.hip)
 # ---------------------------------------------------------------------------
 
