@@ -3,12 +3,18 @@ against what they replace (profiles/PERF.md "Speculative verify").
 
     python tools/verify_bench.py --op     # attention ops alone, 1.3B head shape
     python tools/verify_bench.py --e2e    # generate_speculative vs generate_fast
+    python tools/verify_bench.py --op8    # the int8 cache's verify, per layer call
 
 --op: H 16, D 128, fp16, pages of 64 rows; per (B, T, S) the median over --runs
 rounds of --iters calls each (device events around the batch of calls), the
 three ops alternating inside a round: attention_verify_paged,
 attention_prefill_paged on the same inputs, and T calls of
 attention_decode_paged. KV GB/s = 2 * B * H * S * D * 2 bytes / verify time.
+--op8: the same head shape, fp16 and bf16, T rows behind S cached ones in an
+int8 paged cache; attention_verify_paged_q8, the staged route it replaces
+(kv8_quantize_paged, kv8_load_paged of the S cached rows into a 16-bit staging
+pair, attention_verify_append there) and the 16-bit attention_verify_paged,
+alternating as in --op. Code GB/s = 2 * B * H * S * (D + 4) bytes / int8 time.
 --e2e: random-weight --model-size model, batch 1, --tokens new tokens behind a
 prompt of 128 and 1024, graphs on: generate_fast, generate_speculative with an
 oracle draft (generate_fast's own continuation: every draft accepted, the
@@ -85,6 +91,53 @@ def bench_op(args):
                 print(f"| {B} | {T} | {S} | {v:.1f} | {p:.1f} | {d:.1f} | {gbs:.0f} |", flush=True)
 
 
+def bench_op8(args):
+    dev = torch.device("cuda", 0)
+    H, D, R = 16, 128, 64
+    C = H * D
+    sl = reference.alibi_slopes(H).to(dev)
+    print("| dtype | B | T | S | int8 verify us | staged us | 16-bit verify us | "
+          "int8 / staged | code GB/s |")
+    print("|---|---|---|---|---|---|---|---|---|")
+    for dtype in (torch.float16, torch.bfloat16):
+        for B in (1, 4):
+            for S in (1024, 2048, 4096):
+                M = (S + 16 + R - 1) // R
+                P = B * M + 1
+                bt = (torch.arange(B * M, dtype=torch.int32, device=dev) + 1).view(B, M)
+                kp, vp = (torch.randn(P, H, R, D, device=dev).to(dtype) for _ in range(2))
+                q8 = [reference.quantize_kv_rows(t) for t in (kp, vp)]
+                pools = [q8[0][0], q8[1][0], q8[0][1], q8[1][1]]
+                stage = [torch.zeros(B, H, M * R, D, device=dev, dtype=dtype) for _ in range(2)]
+                start = torch.full((B,), S, dtype=torch.int32, device=dev)
+                for T in (5, 16):
+                    qkv = torch.randn(B, T, 3 * C, device=dev).to(dtype)
+                    lens = torch.full((B,), T, dtype=torch.int32, device=dev)
+
+                    def native():
+                        ops.attention_verify_paged_q8(qkv, *pools, H, sl, bt, lens, start)
+
+                    def staged():
+                        ops.kv8_quantize_paged(qkv, *pools, bt, lens, start)
+                        ops.kv8_load_paged(*pools, bt, start, *stage)
+                        ops.attention_verify_append(qkv, *stage, H, sl, lens, start)
+
+                    def wide():
+                        ops.attention_verify_paged(qkv, kp, vp, H, sl, bt, lens, start)
+
+                    fns = (native, staged, wide)
+                    for f in fns:
+                        timed(f, 5)
+                    res = [[], [], []]
+                    for _ in range(args.runs):
+                        for i, f in enumerate(fns):
+                            res[i].append(timed(f, args.iters))
+                    n, s, w = (statistics.median(r) for r in res)
+                    gbs = 2 * B * H * S * (D + 4) / (n * 1e-6) / 1e9
+                    print(f"| {str(dtype)[6:]} | {B} | {T} | {S} | {n:.1f} | {s:.1f} | {w:.1f} | "
+                          f"{n / s:.2f} | {gbs:.0f} |", flush=True)
+
+
 def bench_e2e(args):
     from zero_transformer_amd.models.inference import (
         generate_fast, generate_speculative, model_getter)
@@ -136,6 +189,7 @@ def bench_e2e(args):
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--op", action="store_true")
+    p.add_argument("--op8", action="store_true")
     p.add_argument("--e2e", action="store_true")
     p.add_argument("--model-size", default="1_3b_2048")
     p.add_argument("--tokens", type=int, default=128)
@@ -146,6 +200,8 @@ def main():
     assert torch.cuda.is_available(), "verify_bench needs the GPU"
     if args.op:
         bench_op(args)
+    if args.op8:
+        bench_op8(args)
     if args.e2e:
         bench_e2e(args)
 

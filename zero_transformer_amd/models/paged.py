@@ -53,11 +53,11 @@ class _PagedAttendQ8:
     `k` / `v` with per-row scale pools `k_scale` / `v_scale`, and a 16-bit
     staging pair `stage_k` / `stage_v` (B, H, M*R, D) shared by all layers.
 
-    Decode attends on the codes natively. Prefill and verify quantize the new
+    Decode and verify attend on the codes natively. Prefill quantizes the new
     rows into the pool (which also replaces them in qkv by what the pool now
-    holds), dequantize the rows already cached into the staging pair, and run
-    the contiguous 16-bit kernels there: those append qkv's rows behind the
-    cached ones in the staging pair and attend over both."""
+    holds), dequantizes the rows already cached into the staging pair, and
+    runs the contiguous 16-bit kernel there: it appends qkv's rows behind the
+    cached ones in the staging pair and attends over both."""
 
     def attend_decode(self, layer_idx, qkv, num_head, slopes):
         return ops.attention_decode_paged_q8(
@@ -78,9 +78,10 @@ class _PagedAttendQ8:
             qkv, self.stage_k, self.stage_v, num_head, slopes, lens, start)
 
     def attend_verify(self, layer_idx, qkv, num_head, slopes, lens, start):
-        qkv = self._stage(layer_idx, qkv, lens, start)
-        return ops.attention_verify_append(
-            qkv, self.stage_k, self.stage_v, num_head, slopes, lens, start)
+        return ops.attention_verify_paged_q8(
+            qkv.contiguous(), self.k[layer_idx], self.v[layer_idx],
+            self.k_scale[layer_idx], self.v_scale[layer_idx], num_head, slopes,
+            self.block_table, lens, start)
 
 
 def _view_init(view, cache, slots: Sequence[int], lens) -> None:
@@ -245,8 +246,8 @@ class PagedKVCacheQ8(_PagedAttendQ8, PagedKVCache):
     instead of 2 D. `k` / `v` hold the codes (uint8, u = q + 128), `k_scale` /
     `v_scale` (P, H, R) fp32 one scale per row and head (format and quantizer:
     ops.kv8_quantize_paged). `dtype` is the model's: that of the one staging
-    pair (slots, H, M*R, D) the prefill and verify passes of all layers work
-    in. Allocator, table and lengths are the parent's."""
+    pair (slots, H, M*R, D) the prefill passes of all layers work in.
+    Allocator, table and lengths are the parent's."""
 
     def __init__(self, n_layers: int, slots: int, heads: int, head_dim: int,
                  num_pages: int, page_rows: int, max_pages_per_seq: int,

@@ -748,6 +748,36 @@ def attention_decode_paged_q8(
         qkv.contiguous(), k_pool, v_pool, k_scale, v_scale, slopes, block_table, lens)
 
 
+def attention_verify_paged_q8(
+    qkv: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor,
+    k_scale: torch.Tensor, v_scale: torch.Tensor, num_head: int,
+    slopes: Optional[torch.Tensor], block_table: torch.Tensor,
+    lens: torch.Tensor, start: torch.Tensor,
+) -> torch.Tensor:
+    """attention_verify_paged on an int8 paged KV cache (layout and quantizer
+    as in kv8_quantize_paged): qkv (B,T,3C) contiguous, T <= 16 -> (B,T,C).
+    The K / V columns of rows i < n are quantized into logical rows start[b]+i
+    and replaced in qkv by what the pools then hold, exactly as
+    kv8_quantize_paged does; query row i attends over the values (u - 128) *
+    scale of rows [0, start[b]+i], read from the code pools (no staging
+    cache): K exactly, its scale applied to the fp32 score, V rounded once to
+    qkv's dtype. Rows i >= n are zeros. No host sync; deterministic and
+    independent of R and of the pages the table names. GPU: fp16/bf16,
+    head_dim 32/64/96/128 (R % 64 != 0 or T > 16 raises;
+    ops/csrc/attn_verify_kv8.hip); everything else takes the fp32 reference.
+    Inference only."""
+    assert qkv.is_contiguous(), "attention_verify_paged_q8 writes qkv in place: contiguous only"
+    if not _kv8_on_gpu(qkv, k_pool):
+        return reference.attention_verify_paged_q8(
+            qkv, k_pool, v_pool, k_scale, v_scale, num_head, slopes, block_table,
+            lens, start)
+    assert k_pool.shape[1] == num_head, "k_pool heads != num_head"
+    if slopes is None:
+        slopes = torch.zeros(num_head, dtype=torch.float32, device=qkv.device)
+    return hip_ops().attn_verify_paged_q8(
+        qkv, k_pool, v_pool, k_scale, v_scale, slopes, block_table, lens, start)
+
+
 # ---------------------------------------------------------------------------
 # Fused per-row sampler
 # ---------------------------------------------------------------------------

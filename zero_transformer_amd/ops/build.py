@@ -34,6 +34,7 @@ SOURCES = [
     "attn_paged.hip",
     "attn_verify.hip",
     "attn_kv8.hip",
+    "attn_verify_kv8.hip",
     "attention_bwd.hip",
     "gemm_lt.hip",
     "gemv.hip",
@@ -58,6 +59,7 @@ SOURCE_FLAGS = {
     "gemm_wq_rows.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "attn_verify.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "attn_kv8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "attn_verify_kv8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

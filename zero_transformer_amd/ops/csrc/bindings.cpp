@@ -56,6 +56,9 @@ void kv8_load_paged(at::Tensor k_pool, at::Tensor v_pool, at::Tensor k_scale,
 at::Tensor attn_decode_paged_q8(at::Tensor qkv, at::Tensor k_pool, at::Tensor v_pool,
                                 at::Tensor k_scale, at::Tensor v_scale, at::Tensor slopes,
                                 at::Tensor block_table, at::Tensor lens);
+at::Tensor attn_verify_paged_q8(at::Tensor qkv, at::Tensor k_pool, at::Tensor v_pool,
+                                at::Tensor k_scale, at::Tensor v_scale, at::Tensor slopes,
+                                at::Tensor block_table, at::Tensor lens, at::Tensor start);
 std::vector<at::Tensor> attn_fwd(at::Tensor qkv, at::Tensor slopes, int64_t H,
                                  double p_drop, int64_t seed);
 std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor qkv, at::Tensor slopes,
@@ -127,6 +130,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_decode_paged_q8", &attn_decode_paged_q8,
         "attn_decode_paged on an int8 paged KV pool with per-row scales; "
         "quantizes and appends the new row (gfx950)");
+  m.def("attn_verify_paged_q8", &attn_verify_paged_q8,
+        "attn_verify_paged on an int8 paged KV pool with per-row scales; quantizes "
+        "and appends the new rows, attends on the codes (gfx950 MFMA)");
   m.def("attn_fwd", &attn_fwd, "fused causal ALiBi flash attention fwd (gfx950 MFMA)");
   // fused: -1 = process default (ZTA_BWD_FUSED), 0 = two-kernel dq + dkdv,
   // 1 = single fused kernel (head_dim 128; other dims take the two-kernel path)

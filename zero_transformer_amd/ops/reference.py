@@ -614,6 +614,30 @@ def attention_decode_paged_q8(qkv, k_pool, v_pool, k_scale, v_scale, num_head,
     return out.to(qkv.dtype)
 
 
+def attention_verify_paged_q8(qkv, k_pool, v_pool, k_scale, v_scale, num_head,
+                             slopes, block_table, lens, start) -> torch.Tensor:
+    """attention_prefill_paged on an int8 paged cache, for the few rows of a
+    verify pass: kv8_quantize_paged (which writes the pools and qkv), then
+    sequence b's rows attend over the fp32 values (u - 128) * scale of its
+    logical rows [0, st + n), the new ones included: the contiguous prefill
+    reference on the gathered, dequantized pools."""
+    B, T, C3 = qkv.shape
+    C = C3 // 3
+    S_alloc = block_table.shape[1] * k_pool.shape[2]
+    kv8_quantize_paged(qkv, k_pool, v_pool, k_scale, v_scale, block_table, lens, start)
+    k, v = (dequantize_kv_rows(paged_gather(pool, block_table),
+                               paged_gather(sc.unsqueeze(-1), block_table).squeeze(-1),
+                               torch.float32)
+            for pool, sc in ((k_pool, k_scale), (v_pool, v_scale)))
+    qf = qkv.float()
+    for b in range(B):  # the new rows as the pools hold them, not rounded to qkv's type
+        st = min(max(int(start[b]), 0), S_alloc)
+        n = min(max(int(lens[b]), 0), min(T, S_alloc - st))
+        for col, cache in ((C, k), (2 * C, v)):
+            qf[b, :n, col:col + C] = cache[b, :, st:st + n].transpose(0, 1).reshape(n, C)
+    return attention_prefill_append(qf, k, v, num_head, slopes, lens, start).to(qkv.dtype)
+
+
 # ---------------------------------------------------------------------------
 # Weight-only int4 rows, group-scaled ("W4A16", ops/csrc/gemv_w4.hip)
 # ---------------------------------------------------------------------------
